@@ -24,6 +24,11 @@ Beside `value` the line carries
   search / search_raxml_path   complete tree inferences per second (the other half of BASELINE.json's metric),
   c4_shard (N = 1) / c4_strong (N > 1)   BASELINE config[3]: this GPU's 63-gene share, resp. the 500-gene job dealt by cost
                      over the N ranks with the one gather of result records (BENCH_NO_C4=1 skips it).
+
+--dump-outputs DIR writes what the last timed step returned to its caller, the per-gene lnL of this rank's genes in the
+order of its shard, as float64 .npy: DIR/lnl.npy (the pass behind `value`) and DIR/stored_lnl.npy (the stored traversal);
+with N > 1 rank r writes lnl.rank<r>.npy and stored_lnl.rank<r>.npy.  The genes are seeded, so equal arguments give equal
+inputs on every run and two builds can be compared file by file.  8 bytes per gene: 1 KB for c3.
 """
 import argparse
 import json
@@ -253,6 +258,7 @@ def main():
     ap.add_argument("--stored-only", action="store_true", help="every scoring step of the run is the stored traversal (counter passes of that leg)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--genes", type=int, default=0, help="strong scaling: total genes of the job (default 500 for c4, 128 for c3, 16 for tiny)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the per-gene lnL the last timed step of each scoring leg returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     # N ranks: either torch.distributed.run provides them (WORLD_SIZE set) or this process starts them itself, strictly
@@ -328,7 +334,7 @@ def main():
             nchunks = pd._world_max(nchunks)
         chunks = [list(c) for c in np.array_split(np.arange(len(G)), nchunks)]
         res = {"dt": 0.0, "dt_cold": 0.0, "dt_stored": 0.0, "npat": 0, "nchunks": nchunks, "clock_warmup_steps": 0, "first_step_ms": None,
-               "lnl": [], "stats": None, "stats_stored": None}
+               "lnl": [], "lnl_stored": [], "stats": None, "stats_stored": None}
         for ci, idx in enumerate(chunks):
             sub = [G[i] for i in idx]
             t_first = time.perf_counter()
@@ -385,8 +391,9 @@ def main():
                 assert np.array_equal(lnl_s, out[-1]), "the stored traversal must return the bits of the register-resident one"
                 if ci == 0:
                     ctx.kernel_stats(reset=True)
-                d, _ = timed(steps, True)
+                d, out = timed(steps, True)
                 res["dt_stored"] += d
+                res["lnl_stored"].append(out[-1])
                 if ci == 0:
                     res["stats_stored"] = ctx.kernel_stats(reset=True)
             if batch:
@@ -405,6 +412,11 @@ def main():
     S = score_legs(ctx, genes, gene_ids, args.steps, args.warmup, float(os.environ.get("BENCH_CLOCK_WARMUP_S", "1.5")), not (args.no_stored or args.stored_only))
     ctx.close()
     nchunks, npat, tot_pat, dt = S["nchunks"], S["npat"], S["npat_all"], S["dt"]
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, parts in (("lnl", S["lnl"]), ("stored_lnl", S["lnl_stored"])):
+            if parts:
+                np.save(os.path.join(args.dump_outputs, name + (".rank%d" % rank if world > 1 else "") + ".npy"), np.concatenate(parts))
 
     # second metric of BASELINE.json: complete tree inferences per second (NJ start, model
     # optimisation, NNI hill climbing), every gene of the shard, one batched call
