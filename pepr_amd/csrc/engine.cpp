@@ -131,6 +131,12 @@ void Ctx::toc() {
     if (!profile) return;
     hipEventRecord(pending.back().b, tic_stream ? tic_stream : stream);
 }
+Ctx::Ev Ctx::tic_self(int kind, double bytes, double flops) {
+    stats[kind].launches++; stats[kind].bytes += bytes; stats[kind].flops += flops;
+    if (!profile) return Ev{kind, nullptr, nullptr};
+    pending.push_back(Ev{kind, get_event(), get_event()});
+    return pending.back();
+}
 void Ctx::resolve_events() {
     for (auto &e : pending) {
         float ms = 0;
@@ -274,6 +280,11 @@ int Batch::layout(double alpha, bool score_only) {
     HIPCHK(hipMalloc((void **)&d_scalars, sizeof(double) * scalars_doubles));
     HIPCHK(hipHostMalloc((void **)&h_scalars, sizeof(double) * scalars_doubles, hipHostMallocDefault));
     std::memset(h_scalars, 0, sizeof(double) * scalars_doubles);
+    // The exception: a replayed scoring plan (replay_plan) produces one lnL per gene, and its k_reduce stores that double
+    // straight into mapped, coherent pinned memory -- one 8-byte write per gene at the end of the step instead of a copy
+    // operation queued behind the kernel; the host reads it after the event that follows k_reduce has completed.
+    HIPCHK(hipHostMalloc((void **)&h_plan_lnl, sizeof(double) * n, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostGetDevicePointer((void **)&d_plan_lnl, h_plan_lnl, 0));
     { if (int rc_ = ctx->sync(ctx->stream)) return rc_; }
     if (std::getenv("PML_TRACE")) fprintf(stderr, "[pml] layout: arena %.1f GiB allocated + uploaded in %.1f ms\n", (double)total / (1 << 30), now_ms() - t_alloc0);
     return 0;
@@ -311,6 +322,8 @@ void Batch::destroy() {
     plan = Plan();
     if (h_scalars) hipHostFree(h_scalars);
     if (d_scalars) hipFree(d_scalars);
+    if (h_plan_lnl) hipHostFree(h_plan_lnl);
+    h_plan_lnl = d_plan_lnl = nullptr;
     if (h_chain) hipHostFree(h_chain);
     if (d_chain) hipFree(d_chain);
     if (d_lenpool) hipFree(d_lenpool);
@@ -1150,6 +1163,15 @@ int Batch::run(std::vector<PendingOp> &ops, const std::vector<Tail> &tails) {
         // ordered against the (non-blocking) stream a replay uploads its refreshed requests on -- the late copy then
         // put the recorded rates back under the first replay (DESIGN r02-g: the cause of the rare different optimum)
         HIPCHK(hipMemcpyAsync(P.d, ds, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        // a replay returns one lnL per gene: its reductions write into d_plan_lnl (gene order) instead of the result slots
+        ReduceReq *pred = (ReduceReq *)((char *)P.h + o_red);
+        P.per_gene = neval == genes.size();
+        for (size_t g = 0; P.per_gene && g < neval; ++g) P.per_gene = pred[g].out == d_scalars + 8 * (g * MAXTAIL);      // request g is gene g's
+        if (P.per_gene) {
+            for (size_t g = 0; g < neval; ++g) pred[g].out = d_plan_lnl + g;
+            HIPCHK(hipMemcpyAsync((char *)P.d + o_red, pred, neval * sizeof(ReduceReq), hipMemcpyHostToDevice, ctx->stream));
+        }
+        P.len_seen.assign(genes.size(), {});
         P.o_req = o_req; P.o_ops = o_ops; P.o_runs = o_runs; P.o_red = o_red;
         P.nreq = ireq; P.nruns = nruns; P.neval = neval; P.max_mpad = max_mpad; P.algo_bytes = algo_bytes; P.algo_flops = algo_flops; P.stored = record_stored; P.any_pitch = any_pitch; P.any_chain = any_chain;
         P.rates_seen.resize(genes.size()); for (size_t g = 0; g < genes.size(); ++g) P.rates_seen[g] = genes[g].rates_epoch;
@@ -1167,39 +1189,52 @@ int Batch::replay_plan(double *lnl) {
     Plan &P = plan;
     HIPCHK(hipSetDevice(ctx->device));
     PmatReq *hreq = (PmatReq *)((char *)P.h + P.o_req);
-    std::vector<char> moved(genes.size(), 0);            // rates are rewritten only for genes whose alpha changed
-    for (size_t g = 0; g < genes.size(); ++g) if (P.rates_seen[g] != genes[g].rates_epoch) { moved[g] = 1; P.rates_seen[g] = genes[g].rates_epoch; }
+    // Only genes whose rates (alpha) or branch lengths moved since the descriptors were last refreshed have their requests
+    // visited: the device waits while this runs, and a step with nothing changed goes straight to the launches.  Lengths are
+    // compared as bytes against a copy per gene (2.4 KB for 50 taxa), whoever wrote them.
+    std::vector<char> &moved = P.moved;
+    moved.assign(genes.size(), 0);
+    bool any_moved = false;
+    for (size_t g = 0; g < genes.size(); ++g) {
+        const Gene &G = genes[g];
+        auto &seen = P.len_seen[g];
+        if (P.rates_seen[g] != G.rates_epoch) { moved[g] = 3; P.rates_seen[g] = G.rates_epoch; }
+        if (seen.size() != G.tree.len.size() || std::memcmp(seen.data(), G.tree.len.data(), seen.size() * sizeof seen[0]) != 0) { moved[g] |= 1; seen = G.tree.len; }
+        any_moved = any_moved || moved[g];
+    }
     bool changed = false;                       // lengths and rates already on the device are not uploaded again
-    for (size_t i = 0; i < P.nreq; ++i) {
+    if (any_moved) for (size_t i = 0; i < P.nreq; ++i) {
         const ReqSrc &s = P.src[i];
+        if (!moved[s.gene]) continue;
         const Gene &G = genes[s.gene];
         const double t = G.tree.len[s.v][s.q];
         if (hreq[i].t != t) { hreq[i].t = t; changed = true; }
-        if (moved[s.gene]) { std::memcpy(hreq[i].rates, G.rates, sizeof hreq[i].rates); changed = true; }
+        if (moved[s.gene] & 2) { std::memcpy(hreq[i].rates, G.rates, sizeof hreq[i].rates); changed = true; }
     }
     char *ds = (char *)P.d;
     if (changed) HIPCHK(hipMemcpyAsync(ds + P.o_req, hreq, P.nreq * sizeof(PmatReq), hipMemcpyHostToDevice, ctx->stream));
     const ModelDev *md = pi_mode < 2 ? ctx->d_model[pi_mode] : nullptr;      // per-gene models travel in the requests
-    ctx->tic(K_PMAT, (double)P.nreq * PFRAG * 8);
-    launch_pmat(md, (const PmatReq *)(ds + P.o_req), d_frags, (int)P.nreq, ctx->stream, d_gmodel != nullptr);
-    ctx->toc();
-    ctx->tic(K_NEWVIEW, P.algo_bytes, P.algo_flops);
-    launch_oplist((const NvOp *)(ds + P.o_ops), (const GeneRun *)(ds + P.o_runs), (int)P.nruns, P.max_mpad, P.any_pitch, P.any_chain, ctx->stream);
-    ctx->toc();
-    ctx->tic(K_REDUCE, 0);
-    launch_reduce((const ReduceReq *)(ds + P.o_red), (int)P.neval, ctx->stream);
-    ctx->toc();
+    // the three launches carry their timing events themselves (profile mode): nothing but kernels in the queue
+    Ctx::Ev ev = ctx->tic_self(K_PMAT, (double)P.nreq * PFRAG * 8);
+    launch_pmat(md, (const PmatReq *)(ds + P.o_req), d_frags, (int)P.nreq, ctx->stream, d_gmodel != nullptr, ev.a, ev.b);
+    ev = ctx->tic_self(K_NEWVIEW, P.algo_bytes, P.algo_flops);
+    launch_oplist((const NvOp *)(ds + P.o_ops), (const GeneRun *)(ds + P.o_runs), (int)P.nruns, P.max_mpad, P.any_pitch, P.any_chain, ctx->stream, nullptr, ev.a, ev.b);
+    ev = ctx->tic_self(K_REDUCE, 0);
+    launch_reduce((const ReduceReq *)(ds + P.o_red), (int)P.neval, ctx->stream, ev.a, ev.b);
+    if (!chain) {
+        if (!P.per_gene) { if (int rc = fetch_results(false)) return rc; }      // per gene: k_reduce has written h_plan_lnl itself
+    }
     const double t_launched = now_ms();
     ctx->stats[K_HOST_BUILD].launches++; ctx->stats[K_HOST_BUILD].ms += t_launched - t_begin;
+    for (auto &o : P.outs) genes[o.first].valid[o.second] = 1;       // host bookkeeping while the device works
     if (!chain) {
-        if (int rc = fetch_results(false)) return rc;
         { if (int rc_ = ctx->sync(ctx->stream)) return rc_; }
         HIPCHK(hipGetLastError());
         const double t_done = now_ms();
         ctx->stats[K_HOST_WAIT].launches++; ctx->stats[K_HOST_WAIT].ms += t_done - t_launched;
         ctx->resolve_events();
     }
-    for (auto &o : P.outs) genes[o.first].valid[o.second] = 1;
+    if (P.per_gene && !chain) for (size_t g = 0; g < genes.size(); ++g) res((int)g)[0] = h_plan_lnl[g];
     for (size_t g = 0; g < genes.size(); ++g) lnl[g] = res((int)g)[0];
 #ifndef ABL_KEEP_GOING
     if (!chain) for (size_t g = 0; g < genes.size(); ++g) if (!std::isfinite(lnl[g])) return ctx->fail(-5, "device returned a non-finite likelihood");

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -49,6 +50,9 @@ struct Ctx {
     hipStream_t tic_stream = nullptr;    // stream the next tic/toc pair is recorded on (null = stream)
     void tic(int kind, double bytes, double flops = 0);   // record start (profile mode); bytes / flops = SURVEY 8d per-operation figures
     void toc();                          // record stop
+    // tic + toc for ONE launch that records its own start and end (launch_* start / stop): the pair of events to hand to it
+    // (null when not profiling).  No marker packets between the kernels of a step
+    Ev tic_self(int kind, double bytes, double flops = 0);
     void resolve_events();               // after a stream sync
     int fail(int code, const std::string &msg) { last_error = msg; return code; }
 };
@@ -128,6 +132,7 @@ struct Batch {
     hipEvent_t ev_stagger = nullptr; bool record_stagger = false;   // lane 1 starts one k_oplist behind lane 0
     double *d_scalars = nullptr; double *h_scalars = nullptr;   // 8 doubles per gene and tail slot: device buffer + pinned host mirror
     size_t scalars_doubles = 0, results_used = 0;
+    double *h_plan_lnl = nullptr, *d_plan_lnl = nullptr;         // replayed scoring plans: one lnL per gene in mapped pinned memory (host pointer, device address)
     int fetch_results(bool pooled);                              // enqueue the device -> host copies of the result buffers
     double *d_nsync = nullptr; size_t nsync_cap = 0;             // Newton inter-workgroup sync blocks
     NewtonCtl *d_nctl = nullptr;                                  // [2]: k_newton control block per lane (tickets, abort word)
@@ -151,6 +156,9 @@ struct Batch {
         bool stored = false;                       // recorded with every CLV written (the traversal a search runs) instead of OPF_NO_STORE
         std::vector<ReqSrc> src; std::vector<std::pair<int, int>> outs;
         std::vector<unsigned> rates_seen;          // per gene: rates_epoch the descriptors carry
+        std::vector<std::vector<std::array<double, 3>>> len_seen;   // per gene: the branch lengths the descriptors carry (empty: not compared yet)
+        std::vector<char> moved;                   // replay scratch, per gene: bit 0 lengths, bit 1 rates differ from the descriptors
+        bool per_gene = false;                     // one evaluation per gene in gene order: the reductions write d_plan_lnl
     } plan;
     long cnt_smooth = 0, cnt_nni = 0, cnt_spr = 0, cnt_eval = 0, cnt_passes = 0;   // run() calls by purpose (PML_TRACE)
     // host wall time by phase, ms (PML_TRACE prints them at the end of a search): where the device waits for the host

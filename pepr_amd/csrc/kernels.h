@@ -176,8 +176,12 @@ void launch_gather(const GatherSeg *segs, int nsegs, int max_npat, hipStream_t s
 struct ShReq { const double *l0, *l1, *l2; const int *site2pat; double *out; unsigned long long seed; int nsites, nboot; };
 void launch_sh(const ShReq *reqs, int n, hipStream_t s);
 
+// start / stop (launch_pmat, launch_oplist without ctl, launch_reduce; both or neither): timing events that the kernel's own
+// dispatch records its start and end in.  Unlike hipEventRecord before and after the launch this puts no marker packets into
+// the queue between two kernels (Ctx::tic_self)
 // per_request: the requests carry their own models (PmatReq::md), `model` is ignored
-void launch_pmat(const ModelDev *model, const PmatReq *reqs, double *frags, int n, hipStream_t s, bool per_request = false);
+void launch_pmat(const ModelDev *model, const PmatReq *reqs, double *frags, int n, hipStream_t s, bool per_request = false,
+                 hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // constant fragment sets for the eigen-basis transforms used by the sumtable:
 //   set 0: x_i = sum_s pi_s U[s][i] A[s]     set 1: y_i = sum_j Uinv[i][j] B[j]
 void launch_eigfrags(const ModelDev *model, double *frags2, hipStream_t s);
@@ -185,13 +189,14 @@ void launch_eigfrags(const ModelDev *model, double *frags2, hipStream_t s);
 void launch_eigfrags_n(const ModelDev *models, double *frags2, int n, hipStream_t s);
 // any_pitch: some op has an SK_PITCH side (two more LDS fragment regions are allocated)
 // ctl != null: the launch has fused Newton tails (OPF_FUSED_NEWTON): chained variant, (gene, tile) claimed by ticket
-void launch_oplist(const NvOp *ops, const GeneRun *runs, int nruns, int max_mpad, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl = nullptr);
+void launch_oplist(const NvOp *ops, const GeneRun *runs, int nruns, int max_mpad, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl = nullptr,
+                   hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // workgroups of the fused-Newton op-list kernel the idle device holds at once (2 per CU)
 int fused_oplist_capacity();
 // genes of more than 32 tiles are fused in ONE launch with one ticket partition over the device (default; PML_FUSE_BIG=0: only
 // when the whole launch is resident at once)
 bool fuse_big_genes();
-void launch_reduce(const ReduceReq *reqs, int n, hipStream_t s);
+void launch_reduce(const ReduceReq *reqs, int n, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // tickets: request index per ticket, register-form tickets [0, nreg) then streaming-form [nreg, nreg + nstream)
 void launch_newton(const ModelDev *model, const NewtonReq *reqs, const int *tickets, int nreg, int nstream, NewtonCtl *ctl, hipStream_t s);
 // the no-exchange fallback: one workgroup per listed request (register-form requests first), same bits as the split form

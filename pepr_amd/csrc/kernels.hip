@@ -25,6 +25,7 @@
 // spawned at RAxMLRunner.java:147 and FastTreeRunner.java:94 (newview / evaluate / makenewz of
 // RAxML 7.2.5, SURVEY.md section 8a-11 iii-v).
 #include "kernels.h"
+#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -1697,12 +1698,14 @@ void launch_gather(const GatherSeg *segs, int nsegs, int max_npat, hipStream_t s
     if (nsegs <= 0 || max_npat <= 0) return;
     hipLaunchKernelGGL(k_gather, dim3((unsigned)nsegs, (unsigned)((max_npat + 255) / 256)), dim3(256), 0, s, segs);
 }
-void launch_pmat(const ModelDev *model, const PmatReq *reqs, double *frags, int n, hipStream_t s, bool per_request) {
+// start / stop (kernels.h): the dispatch packet itself carries the timing events -- hipEventRecord around a launch puts two marker
+// packets into the queue, each a barrier the next kernel waits behind
+void launch_pmat(const ModelDev *model, const PmatReq *reqs, double *frags, int n, hipStream_t s, bool per_request, hipEvent_t start, hipEvent_t stop) {
     if (n <= 0) return;
     const int per_block = PMAT_THREADS / 64;                  // one wave per request, persistent beyond 2 waves per SIMD
     const int blocks = std::min((n + per_block - 1) / per_block, 512);
-    if (per_request) hipLaunchKernelGGL(k_pmat<true>, dim3(blocks), dim3(PMAT_THREADS), 0, s, model, reqs, frags, n);
-    else hipLaunchKernelGGL(k_pmat<false>, dim3(blocks), dim3(PMAT_THREADS), 0, s, model, reqs, frags, n);
+    if (per_request) hipExtLaunchKernelGGL(k_pmat<true>, dim3(blocks), dim3(PMAT_THREADS), 0, s, start, stop, 0, model, reqs, frags, n);
+    else hipExtLaunchKernelGGL(k_pmat<false>, dim3(blocks), dim3(PMAT_THREADS), 0, s, start, stop, 0, model, reqs, frags, n);
 }
 void launch_eigfrags(const ModelDev *model, double *frags2, hipStream_t s) {
     hipLaunchKernelGGL(k_eigfrags, dim3(1), dim3(256), 0, s, model, frags2);
@@ -1716,13 +1719,15 @@ static int oplist_variant() {
     return v;
 }
 static long long newton_timeout_ticks();
-static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl);
+static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,
+                              hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 int fused_oplist_capacity();
 bool fuse_big_genes();
-void launch_oplist(const NvOp *ops, const GeneRun *runs, int nruns, int max_mpad, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl) {
+void launch_oplist(const NvOp *ops, const GeneRun *runs, int nruns, int max_mpad, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,
+                   hipEvent_t start, hipEvent_t stop) {
     if (nruns <= 0) return;
     const int bpg = (max_mpad + PAT_PER_WG - 1) / PAT_PER_WG;
-    if (!ctl) { launch_oplist_one(ops, runs, nruns, bpg, false, any_pitch, chained, s, nullptr); return; }
+    if (!ctl) { launch_oplist_one(ops, runs, nruns, bpg, false, any_pitch, chained, s, nullptr, start, stop); return; }
     // Launches with fused Newton tails: the workgroups of a gene WAIT for each other, and slots are claimed by ticket (whoever
     // holds a ticket is running, and so is every holder of a lower ticket of its partition: all genes but the newest are fully
     // staffed).  What is left to the hardware is to place the newest gene's missing tiles when slots come free -- and that it
@@ -1758,7 +1763,8 @@ int fused_oplist_capacity() {
     }();
     return cap;
 }
-static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg_in, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl) {
+static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg_in, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,
+                              hipEvent_t start, hipEvent_t stop) {
     const long long to = newton_timeout_ticks();
     const int bpg = one_part ? -bpg_in : bpg_in;
     const dim3 grid((unsigned)(one_part ? nruns * bpg_in : ((nruns + 7) / 8) * 8 * bpg_in)), block(256);
@@ -1773,7 +1779,7 @@ static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, i
         const size_t lds16 = (size_t)6 * PFRAG * sizeof(double) + 512;
         static const hipError_t big16 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
         if (big16 == hipSuccess) {
-            hipLaunchKernelGGL(k_oplist16, grid, dim3(OPL16_THREADS), lds16, s, ops, runs, nruns, bpg_in);
+            hipExtLaunchKernelGGL(k_oplist16, grid, dim3(OPL16_THREADS), lds16, s, start, stop, 0, ops, runs, nruns, bpg_in);
             return;
         }
         v = 11;
@@ -1794,20 +1800,20 @@ static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, i
     }
     const int ap = any_pitch ? 1 : 0;
     switch (v) {
-        case 0: hipLaunchKernelGGL(k_oplist<0>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 2: hipLaunchKernelGGL(k_oplist<2>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 3: hipLaunchKernelGGL(k_oplist<3>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 5: hipLaunchKernelGGL(k_oplist<5>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 9: hipLaunchKernelGGL(k_oplist<9>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 10: hipLaunchKernelGGL(k_oplist<10>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 11: hipLaunchKernelGGL(k_oplist<11>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 15: hipLaunchKernelGGL(k_oplist<15>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
-        default: hipLaunchKernelGGL(k_oplist<1>, grid, block, lds, s, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 0: hipExtLaunchKernelGGL(k_oplist<0>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 2: hipExtLaunchKernelGGL(k_oplist<2>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 3: hipExtLaunchKernelGGL(k_oplist<3>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 5: hipExtLaunchKernelGGL(k_oplist<5>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 9: hipExtLaunchKernelGGL(k_oplist<9>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 10: hipExtLaunchKernelGGL(k_oplist<10>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 11: hipExtLaunchKernelGGL(k_oplist<11>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        case 15: hipExtLaunchKernelGGL(k_oplist<15>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+        default: hipExtLaunchKernelGGL(k_oplist<1>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
     }
 }
-void launch_reduce(const ReduceReq *reqs, int n, hipStream_t s) {
+void launch_reduce(const ReduceReq *reqs, int n, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_reduce, dim3(n), dim3(256), 0, s, reqs);
+    hipExtLaunchKernelGGL(k_reduce, dim3(n), dim3(256), 0, s, start, stop, 0, reqs);
 }
 static long long newton_timeout_ticks() {
     // wall-clock bound of one exchange wait, in 100 MHz ticks; PML_NEWTON_TIMEOUT_US is the test hook (0 = give up at the
