@@ -696,8 +696,7 @@ int Batch::flush_deferred() {
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return ctx->fail(-5, std::string("kernel launch: ") + hipGetErrorString(e));
     }
 #undef PML_SER
-    static const size_t flush_max = std::getenv("PML_FLUSH_MAX") ? (size_t)std::atoi(std::getenv("PML_FLUSH_MAX")) : 8;      // A-B arm
-    flush_quota = std::min<size_t>(flush_quota * 2, flush_max);
+    flush_quota = std::min<size_t>(flush_quota * 2, 8);
     return 0;
 }
 
@@ -781,18 +780,10 @@ int Batch::run(std::vector<PendingOp> &ops, const std::vector<Tail> &tails) {
     // iterated inside k_oplist<11> on the register-resident sumtable; PML_NO_FUSE=1 is the A-B arm, safe mode (after an exchange
     // gave up) runs unfused through the no-exchange k_newton form
     static const bool fuse_env = std::getenv("PML_NO_FUSE") == nullptr && !(std::getenv("PML_CHAIN") && std::atoi(std::getenv("PML_CHAIN")) == 0);   // PML_CHAIN=0: the plain kernel only
-    // (genes of more than 32 tiles: kernels.hip launch_oplist -- one launch with one ticket partition over the device by default;
-    // with PML_FUSE_BIG=0 only when the whole launch is resident at once: cut into several resident launches a step pays the
-    // Newton latency once per launch, measured slower than un-fused on a C4 shard)
-    bool fuse_ok = fuse_env && !newton_safe_mode();
-    if (fuse_ok && nnewton && !fuse_big_genes()) {
-        int mm = 0; size_t nr = 0;
-        std::vector<char> seen(genes.size(), 0);
-        for (auto &o : ops) if (!seen[o.gene]) { seen[o.gene] = 1; nr += (size_t)nparts[o.gene]; mm = std::max(mm, genes[o.gene].aln.mpad); }
-        for (auto &t : tails) if (!seen[t.gene]) { seen[t.gene] = 1; nr += (size_t)nparts[t.gene]; mm = std::max(mm, genes[t.gene].aln.mpad); }
-        const size_t bpg = (size_t)(mm + TILE_PAT - 1) / TILE_PAT;
-        if (bpg > 32 && nr * bpg > (size_t)fused_oplist_capacity()) fuse_ok = false;
-    }
+    // (genes of more than 32 tiles: kernels.hip launch_oplist -- one launch with one ticket partition over the device.  Fusing
+    // them only when the whole launch is resident at once, cut into several resident launches, paid the Newton latency once per
+    // launch and measured slower than un-fused on a C4 shard)
+    const bool fuse_ok = fuse_env && !newton_safe_mode();
     std::vector<char> fused_req(nnewton, 0);
     bool any_fused = false;
     std::vector<int> tail_req(ntail, -1);          // tail -> index of its NewtonReq (failure handling below)
@@ -966,9 +957,8 @@ int Batch::run(std::vector<PendingOp> &ops, const std::vector<Tail> &tails) {
                 nr.md = model_of((int)g); nr.tag_base = tag_base; nr.pad0 = 0;
                 // (any number of tails per gene, anywhere in its list: every request has its own exchange block, the gene's workgroups
                 // walk the list in step.  An NNI round -- three tails per internal edge -- then neither writes nor re-reads its pooled
-                // sumtables, 640 B per pattern and tail.  PML_FUSE_MULTI=0: only a gene's single, last tail, the A-B arm)
-                static const bool fuse_multi = !(std::getenv("PML_FUSE_MULTI") && std::atoi(std::getenv("PML_FUSE_MULTI")) == 0);
-                if (fuse_ok && (fuse_multi || (tails_of[key].size() == 1 && t.after < 0)) && !t.patlnl_dev && newton_reg_form(mp)) {
+                // sumtables, 640 B per pattern and tail)
+                if (fuse_ok && !t.patlnl_dev && newton_reg_form(mp)) {
                     d.flags |= OPF_FUSED_NEWTON; d.aux = (const NewtonReq *)(ds + o_newt) + in;
                     fused_req[in] = 1; any_fused = true; any_chain = true;
                 }
@@ -1042,19 +1032,8 @@ int Batch::run(std::vector<PendingOp> &ops, const std::vector<Tail> &tails) {
         // push the transition-matrix fragments and tip tables out of L2 / Infinity Cache, which 8 workgroups per gene re-fetch
         // for every operation -- while the C4 shard (40 tiles per gene: 40 workgroups share each fragment set, and a parent
         // often finds its child's CLV still in the Infinity Cache) takes 10.15 ms instead of 9.18.  Hence by gene size.
-        // PML_NT_STORE=0 never / 2 always / 3 all but results the next operation reads: A-B arms.
-        static const int nt_policy = std::getenv("PML_NT_STORE") ? std::atoi(std::getenv("PML_NT_STORE")) : 1;
-        const bool small_gene = mp <= 16 * TILE_PAT;
-        for (int i = run.op_begin; i < run.op_end; ++i) {
-            NvOp &d = hops[i];
-            if (d.mode != MODE_NEWVIEW || nt_policy == 0 || (nt_policy == 1 && !small_gene)) continue;
-            bool next_reads = false;
-            if (nt_policy == 3 && i + 1 < run.op_end) {
-                const NvOp &nx = hops[i + 1];
-                next_reads = ((nx.flags & 3) == SK_CLV && nx.l.p0 == d.out) || (((nx.flags >> 2) & 3) == SK_CLV && nx.r.p0 == d.out);
-            }
-            if (!next_reads) d.flags |= OPF_NT_STORE;
-        }
+        if (mp <= 16 * TILE_PAT)
+            for (int i = run.op_begin; i < run.op_end; ++i) if (hops[i].mode == MODE_NEWVIEW) hops[i].flags |= OPF_NT_STORE;
     }
 
     if (req_overflow) return ctx->fail(-5, "internal: transition-matrix request bound exceeded");

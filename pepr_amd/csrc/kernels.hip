@@ -372,14 +372,10 @@ __device__ __forceinline__ void load_tip(Operand &o, const unsigned char *__rest
 // acc[st][0/1] = sum_kk frag(c,st,kk) x operand(kk)   (even / odd pattern of the lane).
 // The A fragments are software-pipelined one k-step ahead and fenced with sched_barrier so that
 // hipcc does not hoist all 25 ds_reads (50 VGPRs) in front of the MFMAs.
-#ifndef PML_FRAG_AHEAD
-#define PML_FRAG_AHEAD 1
-#endif
 __device__ __forceinline__ void contract(double (&acc)[5][2], const double *__restrict__ frag_c, const Operand &o) {
-    // the A fragments are requested PML_FRAG_AHEAD k-steps ahead.  Timing-only ablations (profiles/r03_ablation_k_oplist.txt: C3
-    // launch 0.677 ms; fragment reads made free 0.545, tip-table rows free 0.553, CLV loads free 0.645, no per-op barrier 0.687)
-    // say the LDS reads cost 20 % -- but two steps ahead (10 more VGPRs, 3 spills) measures 0.677 vs 0.673: it is not the
-    // latency of one read that is exposed
+    // ONE k-step ahead.  Timing-only ablations (profiles/r03_ablation_k_oplist.txt: C3 launch 0.677 ms; fragment reads made free
+    // 0.545, tip-table rows free 0.553, CLV loads free 0.645, no per-op barrier 0.687) say the LDS reads cost 20 % -- but two
+    // steps ahead (10 more VGPRs, 3 spills) measured 0.677 vs 0.673: it is not the latency of one read that is exposed
 #ifdef ABL_NO_LDS
 // a DIFFERENT constant per fragment element: with one constant for all of them the five state-tile chains of a contraction are
 // identical and the compiler merges them -- four fifths of the MFMAs disappear (the "LDS reads cost 20 %" of the first
@@ -388,23 +384,19 @@ __device__ __forceinline__ void contract(double (&acc)[5][2], const double *__re
 #else
 #define FRAG_RD(x) (x)
 #endif
-    double a[3][5];
+    double a[2][5];
 #pragma unroll
     for (int st = 0; st < 5; ++st) { acc[st][0] = 0.0; acc[st][1] = 0.0; a[0][st] = FRAG_RD(frag_c[(st * 5) * 16]); }
-    if (PML_FRAG_AHEAD >= 2) {
-#pragma unroll
-        for (int st = 0; st < 5; ++st) a[1][st] = FRAG_RD(frag_c[(st * 5 + 1) * 16]);
-    }
 #pragma unroll
     for (int kk = 0; kk < 5; ++kk) {
-        if (kk + PML_FRAG_AHEAD < 5) {
+        if (kk + 1 < 5) {
 #pragma unroll
-            for (int st = 0; st < 5; ++st) a[(kk + PML_FRAG_AHEAD) % 3][st] = FRAG_RD(frag_c[(st * 5 + kk + PML_FRAG_AHEAD) * 16]);
+            for (int st = 0; st < 5; ++st) a[(kk + 1) & 1][st] = FRAG_RD(frag_c[(st * 5 + kk + 1) * 16]);
         }
 #pragma unroll
         for (int st = 0; st < 5; ++st) {
-            acc[st][0] = mfma4(a[kk % 3][st], o.v[kk].x, acc[st][0]);
-            acc[st][1] = mfma4(a[kk % 3][st], o.v[kk].y, acc[st][1]);
+            acc[st][0] = mfma4(a[kk & 1][st], o.v[kk].x, acc[st][0]);
+            acc[st][1] = mfma4(a[kk & 1][st], o.v[kk].y, acc[st][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -412,47 +404,28 @@ __device__ __forceinline__ void contract(double (&acc)[5][2], const double *__re
 
 // st-outer form for the SECOND side: produces one state tile (2 values) at a time so the caller can
 // consume it immediately (multiply with the first side's tile and store): 4 live accumulator
-// registers instead of 40.  Fragments of the next tiles are fetched while the current one runs.
-#ifndef PML_CONSUME_LATE
-#define PML_CONSUME_LATE 0
-#endif
+// registers instead of 40.  Fragments of the next tile are fetched while the current one runs.  (Consuming a tile in the shadow
+// of the next tile's MFMAs instead of behind its own: no gain)
 template <typename F>
 __device__ __forceinline__ void contract_stream(const double *__restrict__ frag_c, const Operand &o, F &&consume) {
-    double a[3][5];
-    double p0 = 0.0, p1 = 0.0;
+    double a[2][5];
 #pragma unroll
     for (int kk = 0; kk < 5; ++kk) a[0][kk] = FRAG_RD(frag_c[kk * 16]);
-    if (PML_FRAG_AHEAD >= 2) {
-#pragma unroll
-        for (int kk = 0; kk < 5; ++kk) a[1][kk] = FRAG_RD(frag_c[(5 + kk) * 16]);
-    }
 #pragma unroll
     for (int st = 0; st < 5; ++st) {
-        if (st + PML_FRAG_AHEAD < 5) {
+        if (st + 1 < 5) {
 #pragma unroll
-            for (int kk = 0; kk < 5; ++kk) a[(st + PML_FRAG_AHEAD) % 3][kk] = FRAG_RD(frag_c[((st + PML_FRAG_AHEAD) * 5 + kk) * 16]);
+            for (int kk = 0; kk < 5; ++kk) a[(st + 1) & 1][kk] = FRAG_RD(frag_c[((st + 1) * 5 + kk) * 16]);
         }
         double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
         for (int kk = 0; kk < 5; ++kk) {
-            acc0 = mfma4(a[st % 3][kk], o.v[kk].x, acc0);
-            acc1 = mfma4(a[st % 3][kk], o.v[kk].y, acc1);
-#if PML_CONSUME_LATE
-            // the previous state tile is consumed (multiply, maximum, store) in the shadow of this tile's MFMAs instead of
-            // behind its own, where the wave would wait for the matrix pipe to drain and then issue VALU work with the pipe idle
-            if (kk == 0 && st > 0) consume(st - 1, p0, p1);
-#endif
+            acc0 = mfma4(a[st & 1][kk], o.v[kk].x, acc0);
+            acc1 = mfma4(a[st & 1][kk], o.v[kk].y, acc1);
         }
-#if PML_CONSUME_LATE
-        p0 = acc0; p1 = acc1;
-#else
         consume(st, acc0, acc1);
-#endif
         __builtin_amdgcn_sched_barrier(0);
     }
-#if PML_CONSUME_LATE
-    consume(4, p0, p1);
-#endif
 }
 
 // cherry operand: product of the two tips' table rows (tables live in global memory, L2-resident:
@@ -480,20 +453,9 @@ __device__ __forceinline__ void load_cherry(Operand &o, const OpSide &sd, unsign
     o.v[3] = (dvec2){a0.b.y * b0.b.y, a1.b.y * b1.b.y};
     o.v[4] = (dvec2){a0.c * b0.c, a1.c * b1.c};
 }
-// the same in two halves, so that the rows of the NEXT category can be in flight during the current category's second contraction
-// (40 VGPRs of raw rows: affordable since the result tile is written straight into X, round 3)
-struct CherryRaw { Rows5 a0, a1, b0, b1; };
-__device__ __forceinline__ void issue_cherry(CherryRaw &r, const OpSide &sd, unsigned ca, unsigned cb, int c, int q) {
-    r.a0 = load_rows(sd.t0, ca & 0xFFu, c, q); r.a1 = load_rows(sd.t0, ca >> 8, c, q);
-    r.b0 = load_rows(sd.t1, cb & 0xFFu, c, q); r.b1 = load_rows(sd.t1, cb >> 8, c, q);
-}
-__device__ __forceinline__ void finish_cherry(Operand &o, const CherryRaw &r) {
-    o.v[0] = (dvec2){r.a0.a.x * r.b0.a.x, r.a1.a.x * r.b1.a.x};
-    o.v[1] = (dvec2){r.a0.a.y * r.b0.a.y, r.a1.a.y * r.b1.a.y};
-    o.v[2] = (dvec2){r.a0.b.x * r.b0.b.x, r.a1.b.x * r.b1.b.x};
-    o.v[3] = (dvec2){r.a0.b.y * r.b0.b.y, r.a1.b.y * r.b1.b.y};
-    o.v[4] = (dvec2){r.a0.c * r.b0.c, r.a1.c * r.b1.c};
-}
+// (Requesting a right-hand cherry's rows early measured slower both ways, profiles/r03_kernel_steps.txt: one category ahead keeps
+// 40 VGPRs of raw rows live through the second contraction, 123 spills; in front of the left contraction of the same category
+// and multiplied behind it, 63 spills, C3 launch 0.60 -> 0.72 ms.)
 // pitchfork operand for category c: ((F_inner . (T_a * T_b)) * T_c), all in registers
 template <bool EARLY = true>
 __device__ __forceinline__ void load_pitch(Operand &o, const OpSide &sd, const double *__restrict__ f_inner,
@@ -515,19 +477,12 @@ __device__ __forceinline__ void load_pitch(Operand &o, const OpSide &sd, const d
     o.v[4] = (dvec2){v[4][0] * r0.c, v[4][1] * r1.c};
 }
 
-// the chained variants unroll the category loop (X[c] with a static index instead of rotating 80 registers per category:
-// C3 scoring launch 0.725 -> 0.693 ms, profiles/r02_ab_chain_unroll.txt); -DPML_CHAIN_UNROLL=0 is the A-B arm
-#ifndef PML_CHAIN_UNROLL
-#define PML_CHAIN_UNROLL 1
-#endif
 // One op on one chunk (32 patterns) of one wave.  All branches on op.* are wave-uniform.
 //   MODE_NEWVIEW : out[c][s] = (P_L,c . L_c)[s] * (P_R,c . R_c)[s], 2^256 rescue, scaling counts
 //   MODE_SUMTABLE: same contraction with the eigen-basis matrices (no rescue), counts = l + r
 //   MODE_EVALUATE: per-pattern ln( 1/4 sum_c sum_s L_c[s] (pi P_c . R_c)[s] ) - counts*256 ln 2
-#ifndef PML_TIPLOOK
-#define PML_TIPLOOK 1
-#endif
-template <bool PREFETCH, bool CHAIN, bool FUSE>
+// CHAIN: register chaining (kernels.h OPF_CHAIN_*); FUSE (implies CHAIN): a sumtable tile may stay in X for newton_fused.
+template <bool CHAIN, bool FUSE>
 __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restrict__ sP, const unsigned char *__restrict__ sT,
                                          int p, int lane, Operand (&X)[4], ivec2 &xsc) {
     // `op` refers to the descriptor in global memory (wave-uniform): fields are fetched by scalar loads
@@ -545,25 +500,18 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
     // fused branch Newton: the sumtable tile is not stored, it stays in X for newton_fused (its counts in xsc)
     const bool fusedN = FUSE && (op.flags & OPF_FUSED_NEWTON) != 0;
     const bool keep = !(CHAIN && (op.flags & OPF_NO_STORE) != 0) && !fusedN;
-    constexpr bool TIPLOOK = PML_TIPLOOK != 0;
-    constexpr bool PF_L = PREFETCH && !CHAIN;       // the chained variants prefetch the right side only (the chained child is the left one; registers)
     // (a plain tip side goes through the MFMA with its 0/1 indicator operand: the matrix pipe has slack and
     // table gathers for it measured slower)
     // The descriptor fields the category loop needs are read ONCE, here, and pinned in SGPRs: a scalar load in the middle of a
     // contraction costs far more than its own latency -- SMEM returns out of order, so the compiler has to wait for it with
     // s_waitcnt lgkmcnt(0), which also drains every LDS fragment read that was requested ahead (78 such drains per operation
     // before; the fragment reads showed up as 20 % of the launch in the ablations, profiles/r03_ablation_k_oplist.txt)
-#ifndef PML_PIN_DESC
-#define PML_PIN_DESC 1
-#endif
     OpSide sdl = op.l, sdr = op.r;
     const int *l_scl = op.l_scl, *r_scl = op.r_scl; int *out_scl = op.out_scl; double *outp = op.out;
-#if PML_PIN_DESC
 #define PML_PIN(x) asm volatile("" : "+s"(x))
     PML_PIN(sdl.p0); PML_PIN(sdl.p1); PML_PIN(sdl.p2); PML_PIN(sdl.t0); PML_PIN(sdl.t1); PML_PIN(sdl.t2); PML_PIN(sdl.f);
     PML_PIN(sdr.p0); PML_PIN(sdr.p1); PML_PIN(sdr.p2); PML_PIN(sdr.t0); PML_PIN(sdr.t1); PML_PIN(sdr.t2); PML_PIN(sdr.f);
     PML_PIN(l_scl); PML_PIN(r_scl); PML_PIN(out_scl); PML_PIN(outp);
-#endif
     gcptr Lp = (gcptr)sdl.p0, Rp = (gcptr)sdr.p0;
     gptr O = (gptr)outp;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)outp, 0, 0x7FFFFFFF, 0x00020000);   // raw buffer over the output CLV
@@ -600,56 +548,29 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
     // already in LDS (A-fragment order: P[4 st + i][4 kk + k] at (st*5 + kk)*16 + k*4 + i) -- 5 LDS reads per pattern and
     // category instead of 25 reads + 50 MFMAs, the same bits (the MFMA adds exact zeros).  Ambiguity codes and gaps (sums of
     // columns) keep the MFMA path for the whole wave, so a pattern's bits do not depend on which path its wave took.
-    const bool lookL = TIPLOOK && mode < MODE_EVALUATE && lk == SK_TIP && !__any((cl & 0xFFu) >= 20u || (cl >> 8) >= 20u);
-    const bool lookR = TIPLOOK && mode < MODE_EVALUATE && rk == SK_TIP && !__any((cr & 0xFFu) >= 20u || (cr >> 8) >= 20u);
+    const bool lookL = mode < MODE_EVALUATE && lk == SK_TIP && !__any((cl & 0xFFu) >= 20u || (cl >> 8) >= 20u);
+    const bool lookR = mode < MODE_EVALUATE && rk == SK_TIP && !__any((cr & 0xFFu) >= 20u || (cr >> 8) >= 20u);
     const double *tL0 = sP + ((cl & 0xFFu) >> 2) * 16 + (cl & 3u) * 4 + q, *tL1 = sP + ((cl >> 8) >> 2) * 16 + ((cl >> 8) & 3u) * 4 + q;
     const double *tR0 = sP + PFRAG + ((cr & 0xFFu) >> 2) * 16 + (cr & 3u) * 4 + q, *tR1 = sP + PFRAG + ((cr >> 8) >> 2) * 16 + ((cr >> 8) & 3u) * 4 + q;
-    Operand curL, curR, nxtL, nxtR;
-    CherryRaw rawR;
+    Operand curL, curR;
     if (lk == SK_TIP && !lookL) load_tip(curL, sT, cl, q);
     else if (lk == SK_CLV && !chL) load_clv(curL, Lp, lane_off, rowbytes, 0);      // evaluate: left side in output layout
     if (rk == SK_TIP && !lookR) load_tip(curR, sT, cr, q);
     else if (rk == SK_CLV && !chR) load_clv(curR, Rp, lane_off, rowbytes, 0);
-    constexpr int CAT_UNROLL = (CHAIN && PML_CHAIN_UNROLL) ? NCAT : 1;
+    // A chained kernel unrolls the category loop: X[c] with a static index, a result tile written straight into X[c] and a
+    // chained side contracted straight out of it.  (Rotating X once per category in a rolled loop: C3 scoring launch 0.725 ->
+    // 0.693 ms unrolled, profiles/r02_ab_chain_unroll.txt; copying a chained side into the operand registers first is 10
+    // v_mov_b64 per category and side, at the 12 cycles a wave pays per double-precision VALU instruction, tools/ubench_f64.hip.)
+    // The fused-Newton kernel keeps the copy: chained operands read in place there are 188 spills, NNI search 217 -> 202
+    // gene-trees/s.
+    constexpr bool DIRECT_IN = CHAIN && !FUSE;
+    constexpr int CAT_UNROLL = CHAIN ? NCAT : 1;
 #pragma unroll CAT_UNROLL
     for (int c = 0; c < NCAT; ++c) {
-        Operand Y;                                            // CHAIN: this category of the result
-        // (fully unrolled: a chained side is contracted straight out of X[c] -- its own code path below -- instead of being copied
-        // into the operand registers first: 10 v_mov_b64 per category and side, at the 12 cycles a wave pays per double-precision
-        // VALU instruction, tools/ubench_f64.hip)
-        constexpr bool DIRECT = CHAIN && CAT_UNROLL == NCAT;        // results are written straight into X[c]
-#ifndef PML_DIRECT_FUSE
-#define PML_DIRECT_FUSE 0
-#endif
-        constexpr bool DIRECT_IN = DIRECT && (!FUSE || PML_DIRECT_FUSE);    // chained operands are read straight from X[c]
-        if (CHAIN && !DIRECT_IN) {
-            if (CAT_UNROLL == NCAT) { if (chL) curL = X[c]; if (chR) curR = X[c]; }
-            else { if (chL) curL = X[0]; if (chR) curR = X[0]; }     // X is rotated once per category: X[0] is category c
-        }
-        if (PREFETCH && c + 1 < NCAT) {                       // software prefetch of the next category
-            if (PF_L && lk == SK_CLV && !chL) load_clv(nxtL, Lp, lane_off, rowbytes, c + 1);
-            if (rk == SK_CLV && !chR) load_clv(nxtR, Rp, lane_off, rowbytes, c + 1);
-        }
-        // PML_PF_ROWS (A-B arms, both measured slower, profiles/r03_kernel_steps.txt): 1 = a right-hand cherry's rows requested one
-        // category ahead (40 VGPRs of raw rows live through the second contraction: 123 spills), 2 = requested in front of the
-        // left contraction of the same category and multiplied behind it (63 spills, 0.60 -> 0.72 ms)
-#ifndef PML_PF_ROWS
-#define PML_PF_ROWS 0
-#endif
-        constexpr bool PF_ROWS = PML_PF_ROWS && DIRECT && !FUSE;
-        const bool pfR = PF_ROWS && rk == SK_CHERRY && lk == SK_CLV && mode < MODE_EVALUATE;     // right-hand cherry next to a CLV: rows requested early
-        // (first thing in the category: the 40 raw-row registers die here, before the left side builds its own operand)
-#if PML_PF_ROWS == 1
-        if (pfR) { if (c == 0) issue_cherry(rawR, sdr, cr, cr2, 0, q); finish_cherry(curR, rawR); }
-#else
-        // PML_PF_ROWS == 2: the rows of THIS category are requested here and multiplied behind the left contraction, whose 50 MFMAs
-        // cover most of their L2 round trip; nothing stays live across categories
-        if (pfR) issue_cherry(rawR, sdr, cr, cr2, c, q);
-#endif
+        if (FUSE) { if (chL) curL = X[c]; if (chR) curR = X[c]; }
         if (lk == SK_CHERRY) load_cherry(curL, sdl, cl, cl2, c, q);
         else if (lk == SK_PITCH) load_pitch<!FUSE>(curL, sdl, fLi, cl, cl2, cl3, c, q);
-        if (pfR) {}
-        else if (rk == SK_CHERRY) load_cherry(curR, sdr, cr, cr2, c, q);
+        if (rk == SK_CHERRY) load_cherry(curR, sdr, cr, cr2, c, q);
         else if (rk == SK_PITCH) { if (both_pitch) load_pitch<!FUSE>(curR, sdr, fRg, cr, cr2, cr3, c, q); else load_pitch<!FUSE>(curR, sdr, fLi, cr, cr2, cr3, c, q); }
         if (mode >= MODE_EVALUATE) {
             if (DIRECT_IN && chL) contract_stream(fR + c * 25 * 16, curR, [&](int st, double y0, double y1) { site0 += X[c].v[st].x * y0; site1 += X[c].v[st].y * y1; });
@@ -671,18 +592,13 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
                 for (int st = 0; st < 5; ++st) { aL[st][0] = tL0[c * 400 + st * 80]; aL[st][1] = tL1[c * 400 + st * 80]; }
             } else if (DIRECT_IN && chL) contract(aL, fL + c * 25 * 16, X[c]);
             else contract(aL, fL + c * 25 * 16, curL);
-#if PML_PF_ROWS == 1
-            if (pfR && c + 1 < NCAT) issue_cherry(rawR, sdr, cr, cr2, c + 1, q);
-#else
-            if (pfR) finish_cherry(curR, rawR);
-#endif
             auto emit = [&](int st, double y0, double y1) {
                 const double o0 = aL[st][0] * y0, o1 = aL[st][1] * y1;
                 mx0 = max(mx0, (unsigned)__double2hiint(o0)); mx1 = max(mx1, (unsigned)__double2hiint(o1));
-                // fully unrolled: the result tile goes straight into X[c] (the left contraction of this category, the only reader
-                // of the old X[c], is complete) -- for sumtable operations too, which therefore END a chain (engine.cpp: nothing is
-                // chained from across a sumtable tail)
-                if (CHAIN) { if (DIRECT) X[c].v[st] = (dvec2){o0, o1}; else Y.v[st] = (dvec2){o0, o1}; }
+                // the result tile goes straight into X[c] (the left contraction of this category, the only reader of the old
+                // X[c], is complete) -- for sumtable operations too, which therefore END a chain (engine.cpp: nothing is chained
+                // from across a sumtable tail)
+                if (CHAIN) X[c].v[st] = (dvec2){o0, o1};
                 if (!keep) return;
 #ifdef ABL_NO_STORE
                 return;
@@ -700,16 +616,11 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
                 for (int st = 0; st < 5; ++st) emit(st, tR0[c * 400 + st * 80], tR1[c * 400 + st * 80]);
             } else contract_stream(fR + c * 25 * 16, curR, emit);
         }
-        if (CHAIN && !DIRECT) {
-            if (mode == MODE_NEWVIEW) { X[0] = X[1]; X[1] = X[2]; X[2] = X[3]; X[3] = Y; }
-            else if (chL || chR) { const Operand t = X[0]; X[0] = X[1]; X[1] = X[2]; X[2] = X[3]; X[3] = t; }   // a tail leaves X as it was
-        }
+        // the next category's CLV rows are requested here, behind this category's contractions.  (The right-hand rows one category
+        // ahead in the chained kernel: 0.599 against 0.595 ms per C3 launch, 28 bytes of scratch)
         if (c + 1 < NCAT) {
-            if (PREFETCH) { if (PF_L && lk == SK_CLV && !chL) curL = nxtL; if (rk == SK_CLV && !chR) curR = nxtR; }
-            if (!PF_L) { if (lk == SK_CLV && !chL) load_clv(curL, Lp, lane_off, rowbytes, c + 1); }
-            if (!PREFETCH) {
-                if (rk == SK_CLV && !chR) load_clv(curR, Rp, lane_off, rowbytes, c + 1);
-            }
+            if (lk == SK_CLV && !chL) load_clv(curL, Lp, lane_off, rowbytes, c + 1);
+            if (rk == SK_CLV && !chR) load_clv(curR, Rp, lane_off, rowbytes, c + 1);
         }
     }
 
@@ -760,20 +671,9 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
 
 // ------------------------------------------------------------------------------------------
 // k_oplist: workgroup (gene, pattern block of 128) executes the gene's op list in order.
-// VARIANT bit0: low-register form (no category prefetch)
-//         bit1: double-buffered fragment staging by LDS-DMA (one barrier per op)
 // ------------------------------------------------------------------------------------------
 constexpr int PAT_PER_WG = 4 * PAT_PER_WAVE;   // 128
 constexpr int TIPTAB = NCODES * NS;            // 460 bytes (0/1 indicators)
-
-__device__ __forceinline__ void stage_frags_dma(const NvOp &op, double *dst, int lane, int wave) {
-    // 2*PFRAG doubles = 25 KiB = 25 wave-instructions of 1 KiB (16 B per lane)
-    for (int i = wave; i < 25; i += 4) {
-        const int e = i * 128 + lane * 2;      // element index of this lane's 16 bytes in [left|right]
-        const double *g = (e < PFRAG) ? (op.pl ? op.pl : op.pr) + e : (op.pr ? op.pr : op.pl) + (e - PFRAG);
-        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)g, (__attribute__((address_space(3))) void *)(dst + i * 128), 16, 0, 0);
-    }
-}
 
 #ifndef PML_CHAIN_WAVES
 #define PML_CHAIN_WAVES 2
@@ -901,24 +801,25 @@ extern "C" void pml_abl_optime(unsigned long long *out, int reset) {
 }
 namespace pml {
 #endif
-template <int VARIANT>
-// VARIANT 5 = variant 1 compiled for 3 waves/SIMD (168 VGPRs, no spills)
-// VARIANT 9 = variant 1 with register chaining (kernels.h OPF_CHAIN_*): 80 more live VGPRs, 2 waves/SIMD
-// VARIANT 11 = 9 + double-buffered fragment staging by LDS-DMA, three regions per parity (2 workgroups per CU leave 80 KB each)
-// VARIANT 15 = 11 + fused branch Newton (OPF_FUSED_NEWTON) and ticketed slots: the launches of the search that carry Newton
-//              tails; a variant of its own so that the Newton code (exp, log, exchange) costs the scoring kernel no register
-__global__ __launch_bounds__(256, (VARIANT == 1) ? 4 : (VARIANT >= 8) ? PML_CHAIN_WAVES : 3) void k_oplist(
+// CHAIN: register chaining (kernels.h OPF_CHAIN_*): 80 more live VGPRs, 2 waves per SIMD instead of 4.
+// DBUF (chained kernels): the NEXT operation's fragment sets are staged by LDS-DMA while this one runs, one barrier per operation;
+//       three regions per parity = 77 KB of dynamic LDS (2 workgroups per CU leave 80 KB each).  Without it: one set of regions,
+//       filled by the workgroup's own loads between two barriers.
+// FUSE (on top of both): fused branch Newton (OPF_FUSED_NEWTON) and ticketed slots.
+// Four instantiations exist (names below); launch_oplist_one chooses among them.  (Measured against them and dropped: one
+// pattern per lane at 4 waves per SIMD with chaining kept, 0.797 against 0.676 ms per C3 scoring launch, 46 spills, DESIGN.md 9
+// r03-g; the plain kernel at 3 waves per SIMD, with CLV rows one category ahead or with LDS-DMA staging, never the default.
+// DESIGN.md 4 says where their source can be read.)
+template <bool CHAIN, bool DBUF, bool FUSE>
+__global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
         const NvOp *__restrict__ ops, const GeneRun *__restrict__ runs, int nruns, int blocks_per_gene, int any_pitch,
         NewtonCtl *ctl, long long timeout_ticks) {
+    static_assert(CHAIN || !DBUF, "LDS-DMA staging exists for the chained kernels only");
+    static_assert(!FUSE || (CHAIN && DBUF), "the fused-Newton kernel is the scoring kernel plus the Newton code");
 #ifdef PML_OPTIME
     const long long t_life0 = clock64();
 #endif
-    constexpr bool PREFETCH = !(VARIANT & 1);
-    constexpr bool CHAIN = VARIANT >= 8;                  // 8..11, 15: bit 0 / bit 1 as above, three LDS regions per parity
-    constexpr bool FUSE = VARIANT == 15;
-    constexpr bool DBUF3 = CHAIN && (VARIANT & 2) != 0;
-    constexpr bool DBUF = ((VARIANT & 2) != 0 && VARIANT < 4) || DBUF3;
-    constexpr int PARITY_STRIDE = (DBUF3 ? 3 : 2) * PFRAG;
+    constexpr int PARITY_STRIDE = 3 * PFRAG;
     Operand X[4]; ivec2 xsc = {0, 0};
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -927,7 +828,7 @@ __global__ __launch_bounds__(256, (VARIANT == 1) ? 4 : (VARIANT >= 8) ? PML_CHAI
     // dynamic LDS: [left|right] fragments (x2 when double-buffered) [+ left-inner|right-inner fragments of
     // pitchfork sides when the launch has any] + the float tip-indicator table
     extern __shared__ double sP[];
-    const int nfrag_regions = DBUF3 ? 6 : (DBUF ? 4 : 2) + (any_pitch ? 1 : 0);
+    const int nfrag_regions = DBUF ? 6 : 2 + (any_pitch ? 1 : 0);
     unsigned char *sT = reinterpret_cast<unsigned char *>(sP + nfrag_regions * PFRAG);
     // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share
     // an XCD and its L2), so all pattern blocks of one gene get the same blockIdx % 8: the gene's
@@ -974,7 +875,7 @@ __global__ __launch_bounds__(256, (VARIANT == 1) ? 4 : (VARIANT >= 8) ? PML_CHAI
     const long long t_start1 = clock64();        // slot claimed, run descriptor read
 #endif
     for (int i = tid; i < TIPTAB; i += 256) sT[i] = (unsigned char)((code_mask(i / NS) >> (i % NS)) & 1u);
-    if (DBUF) { if (DBUF3) stage_frags_dma3(ops[run.op_begin], sP, lane, wave); else stage_frags_dma(ops[run.op_begin], sP, lane, wave); }
+    if (DBUF) stage_frags_dma3(ops[run.op_begin], sP, lane, wave);
     __syncthreads();
 #ifdef PML_OPTIME
     const long long t_start2 = clock64();        // tip table filled, first fragment sets staged and landed
@@ -986,10 +887,7 @@ __global__ __launch_bounds__(256, (VARIANT == 1) ? 4 : (VARIANT >= 8) ? PML_CHAI
         if (DBUF) {
             const int par = (oi - run.op_begin) & 1;
             buf = sP + par * PARITY_STRIDE;
-            if (oi + 1 < run.op_end) {
-                if (DBUF3) stage_frags_dma3(ops[oi + 1], sP + (par ^ 1) * PARITY_STRIDE, lane, wave);
-                else stage_frags_dma(ops[oi + 1], sP + (par ^ 1) * PARITY_STRIDE, lane, wave);
-            }
+            if (oi + 1 < run.op_end) stage_frags_dma3(ops[oi + 1], sP + (par ^ 1) * PARITY_STRIDE, lane, wave);
         } else {
             if (oi > run.op_begin) __syncthreads();      // previous op: LDS reads and global stores complete
             const double2 *gl = reinterpret_cast<const double2 *>(op.pl);
@@ -1013,7 +911,7 @@ __global__ __launch_bounds__(256, (VARIANT == 1) ? 4 : (VARIANT >= 8) ? PML_CHAI
         const long long t_op0 = clock64();
 #endif
 #ifndef ABL_NO_OP        // timing-only ablation: the shell alone (descriptor reads, fragment staging, barriers)
-        if (active) chunk_op<PREFETCH, CHAIN, FUSE>(op, buf, sT, p, lane, X, xsc);
+        if (active) chunk_op<CHAIN, FUSE>(op, buf, sT, p, lane, X, xsc);
 #endif
 #ifdef PML_OPTIME
         if (lane == 0 && active) {
@@ -1052,237 +950,13 @@ __global__ __launch_bounds__(256, (VARIANT == 1) ? 4 : (VARIANT >= 8) ? PML_CHAI
     leave();
 }
 
-// ------------------------------------------------------------------------------------------
-// k_oplist16 (round 3): the chained op-list kernel with ONE pattern per lane -- a wave owns 16 patterns instead of 32.
-// Why: k_oplist<11> needs 256 VGPRs (the chained result alone is 80), i.e. 2 waves per SIMD, and its MFMA bursts are separated
-// by L2 / HBM round trips that two waves cannot hide (matrix pipe 34 % busy, waves 47 % in s_waitcnt).  With one pattern per lane
-// every per-pattern quantity halves (chained result 40 VGPRs, operands 10, left result 10): the kernel fits 128 VGPRs = 4 waves
-// per SIMD with register chaining KEPT.  A workgroup is still one 128-pattern tile, now 8 waves (512 threads) sharing the staged
-// fragment sets; two workgroups per CU = the same 256 patterns in flight per CU, as 16 waves instead of 8.  The price: an A
-// fragment read from LDS feeds one MFMA instead of two (LDS reads = MFMA count: the LDS pipe is as busy as the matrix pipe).
-// Arithmetic per pattern is unchanged (the four blocks of v_mfma_f64_4x4x4_4b are independent 4x4x4 products): same bits.
-// RESULT (same box, rotated order, profiles/r03_ab_k_oplist16.txt): SLOWER -- 0.797 ms per C3 scoring launch against 0.676 ms of
-// k_oplist<11> (stored traversal 0.93 vs 0.77).  The kernel does not fit its 128 VGPRs (46 spills, in prologue and epilogue), the
-// fragment reads cannot be software-pipelined inside that budget (each k-step waits for its five ds_reads: 480 s_waitcnt per
-// 500 MFMAs), and twice the LDS reads per MFMA are exposed instead of hidden.  Kept as an A-B arm (PML_CHAIN_VARIANT=16), not used.
-// Lane (j = lane & 15, q = lane >> 4): B operand = CLV[state 4 kk + q][pattern j], D = out[state 4 st + q][pattern j].
-// ------------------------------------------------------------------------------------------
-struct Operand1 { double v[5]; };
-
-__device__ __forceinline__ void load_clv1(Operand1 &o, gcptr base, unsigned lane_off, size_t rowbytes, int c) {
-#pragma unroll
-    for (int kk = 0; kk < 5; ++kk)
-        o.v[kk] = __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS double *>(base + (size_t)(c * NS + kk * 4) * rowbytes + lane_off));
-}
-__device__ __forceinline__ void load_tip1(Operand1 &o, const unsigned char *__restrict__ T, unsigned code, int q) {
-    const unsigned char *t0 = T + code * NS + q;
-#pragma unroll
-    for (int kk = 0; kk < 5; ++kk) o.v[kk] = (double)t0[kk * 4];
-}
-__device__ __forceinline__ void contract1(double (&acc)[5], const double *__restrict__ frag_c, const Operand1 &o) {
-    // no software pipelining of the fragment reads: the ten registers of a second fragment column push the kernel further over
-    // its 128-VGPR budget (58 spills instead of 46) and measured slower (0.827 vs 0.797 ms per C3 launch)
-#pragma unroll
-    for (int st = 0; st < 5; ++st) acc[st] = 0.0;
-#pragma unroll
-    for (int kk = 0; kk < 5; ++kk) {
-        double a[5];
-#pragma unroll
-        for (int st = 0; st < 5; ++st) a[st] = frag_c[(st * 5 + kk) * 16];
-#pragma unroll
-        for (int st = 0; st < 5; ++st) acc[st] = mfma4(a[st], o.v[kk], acc[st]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-template <typename F>
-__device__ __forceinline__ void contract_stream1(const double *__restrict__ frag_c, const Operand1 &o, F &&consume) {
-#pragma unroll
-    for (int st = 0; st < 5; ++st) {
-        double a[5];
-#pragma unroll
-        for (int kk = 0; kk < 5; ++kk) a[kk] = frag_c[(st * 5 + kk) * 16];
-        double acc = 0.0;
-#pragma unroll
-        for (int kk = 0; kk < 5; ++kk) acc = mfma4(a[kk], o.v[kk], acc);
-        consume(st, acc);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-__device__ __forceinline__ void load_cherry1(Operand1 &o, const OpSide &sd, unsigned ca, unsigned cb, int c, int q) {
-    const Rows5 a = load_rows(sd.t0, ca, c, q), b = load_rows(sd.t1, cb, c, q);
-    o.v[0] = a.a.x * b.a.x; o.v[1] = a.a.y * b.a.y; o.v[2] = a.b.x * b.b.x; o.v[3] = a.b.y * b.b.y; o.v[4] = a.c * b.c;
-}
-__device__ __forceinline__ void load_pitch1(Operand1 &o, const OpSide &sd, const double *__restrict__ f_inner,
-                                            unsigned ca, unsigned cb, unsigned cc, int c, int q) {
-    Operand1 w;
-    load_cherry1(w, sd, ca, cb, c, q);
-    double v[5];
-    contract1(v, f_inner + c * 25 * 16, w);
-    const Rows5 r = load_rows(sd.t2, cc, c, q);
-    o.v[0] = v[0] * r.a.x; o.v[1] = v[1] * r.a.y; o.v[2] = v[2] * r.b.x; o.v[3] = v[3] * r.b.y; o.v[4] = v[4] * r.c;
-}
-
-// one op on one chunk of 16 patterns of one wave (the twin of chunk_op<false, true, false>)
-__device__ __forceinline__ void chunk_op1(const NvOp &op, const double *__restrict__ sP, const unsigned char *__restrict__ sT,
-                                          int p, int lane, Operand1 (&X)[4], int &xsc) {
-    const int q = lane >> 4;
-    constexpr size_t rowbytes = (size_t)TILE_PAT * 8;
-    const size_t tabrow = (size_t)op.mpad * 8;
-    const unsigned lane_off = (unsigned)(p >> 7) * (unsigned)(CLV_ROWS * rowbytes) + (unsigned)((size_t)q * rowbytes) + (unsigned)(p & (TILE_PAT - 1)) * 8u;
-    const int lk = op.flags & 3, rk = (op.flags >> 2) & 3;
-    const bool nt_store = (op.flags & OPF_NT_STORE) != 0;
-    const int mode = op.mode;
-    const bool chL = (op.flags & OPF_CHAIN_L) != 0, chR = (op.flags & OPF_CHAIN_R) != 0;
-    const bool keep = (op.flags & OPF_NO_STORE) == 0;
-    gcptr Lp = (gcptr)op.l.p0, Rp = (gcptr)op.r.p0;
-    gptr O = (gptr)op.out;
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)op.out, 0, 0x7FFFFFFF, 0x00020000);
-    const double *fL = sP + (q * 4 + (lane & 3));
-    const double *fR = fL + PFRAG;
-    double mx = 0.0, site = 0.0;
-    unsigned cl = 0, cl2 = 0, cl3 = 0, cr = 0, cr2 = 0, cr3 = 0;
-    const double *fLi = fL + 2 * PFRAG;
-    const double *fRi = (lk == SK_PITCH) ? op.r.f + (q * 4 + (lane & 3)) : fL + 2 * PFRAG;
-    if (lk != SK_CLV) cl = *reinterpret_cast<const GLOBAL_AS unsigned char *>(Lp + p);
-    if (lk >= SK_CHERRY) cl2 = *reinterpret_cast<const GLOBAL_AS unsigned char *>((gcptr)op.l.p1 + p);
-    if (lk == SK_PITCH) cl3 = *reinterpret_cast<const GLOBAL_AS unsigned char *>((gcptr)op.l.p2 + p);
-    if (rk != SK_CLV) cr = *reinterpret_cast<const GLOBAL_AS unsigned char *>(Rp + p);
-    if (rk >= SK_CHERRY) cr2 = *reinterpret_cast<const GLOBAL_AS unsigned char *>((gcptr)op.r.p1 + p);
-    if (rk == SK_PITCH) cr3 = *reinterpret_cast<const GLOBAL_AS unsigned char *>((gcptr)op.r.p2 + p);
-    // plain tip sides by look-up of the fragment set's column (same rule as chunk_op: the whole wave or not at all)
-    const bool lookL = mode < MODE_EVALUATE && lk == SK_TIP && !__any(cl >= 20u);
-    const bool lookR = mode < MODE_EVALUATE && rk == SK_TIP && !__any(cr >= 20u);
-    const double *tL = sP + (cl >> 2) * 16 + (cl & 3u) * 4 + q;
-    const double *tR = sP + PFRAG + (cr >> 2) * 16 + (cr & 3u) * 4 + q;
-    Operand1 curL, curR;
-    if (lk == SK_TIP && !lookL) load_tip1(curL, sT, cl, q);
-    else if (lk == SK_CLV && !chL) load_clv1(curL, Lp, lane_off, rowbytes, 0);
-    if (rk == SK_TIP && !lookR) load_tip1(curR, sT, cr, q);
-    else if (rk == SK_CLV && !chR) load_clv1(curR, Rp, lane_off, rowbytes, 0);
-#pragma unroll
-    for (int c = 0; c < NCAT; ++c) {
-        Operand1 Y;
-        if (chL) curL = X[c];
-        if (chR) curR = X[c];
-        if (lk == SK_CHERRY) load_cherry1(curL, op.l, cl, cl2, c, q);
-        else if (lk == SK_PITCH) load_pitch1(curL, op.l, fLi, cl, cl2, cl3, c, q);
-        if (rk == SK_CHERRY) load_cherry1(curR, op.r, cr, cr2, c, q);
-        else if (rk == SK_PITCH) load_pitch1(curR, op.r, fRi, cr, cr2, cr3, c, q);
-        if (mode >= MODE_EVALUATE) {
-            contract_stream1(fR + c * 25 * 16, curR, [&](int st, double y) { site += curL.v[st] * y; });
-            if (mode == MODE_EVALUATE_CAT) {
-                double a = site;
-                a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
-                if (q == 0) *reinterpret_cast<GLOBAL_AS double *>(O + (size_t)c * tabrow + 8 * p) = a;
-                site = 0.0;
-            }
-        } else {
-            double aL[5];
-            if (lookL) {
-#pragma unroll
-                for (int st = 0; st < 5; ++st) aL[st] = tL[c * 400 + st * 80];
-            } else contract1(aL, fL + c * 25 * 16, curL);
-            auto emit = [&](int st, double y) {
-                const double o = aL[st] * y;
-                mx = fmax(mx, o);
-                Y.v[st] = o;
-                if (!keep) return;
-                typedef unsigned uvec2 __attribute__((ext_vector_type(2)));
-                const uvec2 bits = __builtin_bit_cast(uvec2, o);
-                const int soff = (c * NS + st * 4) * (int)rowbytes;
-                if (nt_store) __builtin_amdgcn_raw_buffer_store_b64(bits, orsrc, lane_off, soff, 2);
-                else __builtin_amdgcn_raw_buffer_store_b64(bits, orsrc, lane_off, soff, 0);
-            };
-            if (lookR) {
-#pragma unroll
-                for (int st = 0; st < 5; ++st) emit(st, tR[c * 400 + st * 80]);
-            } else contract_stream1(fR + c * 25 * 16, curR, emit);
-        }
-        if (mode == MODE_NEWVIEW) X[c] = Y;
-        if (c + 1 < NCAT) {
-            if (lk == SK_CLV && !chL) load_clv1(curL, Lp, lane_off, rowbytes, c + 1);
-            if (rk == SK_CLV && !chR) load_clv1(curR, Rp, lane_off, rowbytes, c + 1);
-        }
-    }
-    int sc = 0;
-    if (q == 0) {
-        if (lk == SK_CLV) { if (chL) sc += xsc; else sc += *reinterpret_cast<const GLOBAL_AS int *>((gcptr)op.l_scl + 4 * p); }
-        if (rk == SK_CLV) { if (chR) sc += xsc; else sc += *reinterpret_cast<const GLOBAL_AS int *>((gcptr)op.r_scl + 4 * p); }
-    }
-    if (mode == MODE_NEWVIEW) {
-        mx = fmax(mx, __shfl_xor(mx, 16)); mx = fmax(mx, __shfl_xor(mx, 32));
-        const bool n0 = mx < TWO_M256;
-        if (__any(n0)) {                     // rare: numerical rescue of underflowing patterns
-            const double f0 = n0 ? TWO_P256 : 1.0;
-#pragma unroll
-            for (int c = 0; c < NCAT; ++c)
-#pragma unroll
-                for (int k = 0; k < 5; ++k) X[c].v[k] *= f0;
-            if (keep && n0) {
-#pragma unroll 1
-                for (int r = 0; r < NCAT * 5; ++r) {
-                    GLOBAL_AS double *ptr = reinterpret_cast<GLOBAL_AS double *>(O + (size_t)((r / 5) * NS + (r % 5) * 4) * rowbytes + lane_off);
-                    *ptr = *ptr * TWO_P256;
-                }
-            }
-        }
-        if (q == 0) { sc += n0 ? 1 : 0; if (keep) *reinterpret_cast<GLOBAL_AS int *>((gptr)op.out_scl + 4 * p) = sc; }
-        xsc = sc;
-    } else if (mode == MODE_SUMTABLE || mode == MODE_EVALUATE_CAT) {
-        if (q == 0) *reinterpret_cast<GLOBAL_AS int *>((gptr)op.out_scl + 4 * p) = sc;
-    } else {
-        site += __shfl_xor(site, 16); site += __shfl_xor(site, 32);
-        if (q == 0) *reinterpret_cast<GLOBAL_AS double *>(O + 8 * p) = log(site * 0.25) - sc * LOG_2_256;
-    }
-}
-
-constexpr int OPL16_THREADS = 512;                     // 8 waves x 16 patterns = one 128-pattern tile
-__global__ __launch_bounds__(OPL16_THREADS, 4) void k_oplist16(const NvOp *__restrict__ ops, const GeneRun *__restrict__ runs, int nruns,
-                                                               int blocks_per_gene) {
-    Operand1 X[4]; int xsc = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) X[c].v[k] = 0.0;
-    extern __shared__ double sP[];                      // 2 parities x [left | right | inner] fragment sets + the tip-indicator table
-    constexpr int PARITY_STRIDE = 3 * PFRAG;
-    unsigned char *sT = reinterpret_cast<unsigned char *>(sP + 6 * PFRAG);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int gi = xcd + 8 * (slot / blocks_per_gene), blk = slot % blocks_per_gene;
-    if (gi >= nruns) return;
-    const GeneRun run = runs[gi];
-    if (run.op_begin >= run.op_end) return;
-    const int mpad = ops[run.op_begin].mpad;
-    if (blk * TILE_PAT >= mpad) return;
-    const int p = blk * TILE_PAT + wave * 16 + (lane & 15);
-    const bool active = blk * TILE_PAT + wave * 16 < mpad;
-    auto stage = [&](const NvOp &op, double *dst) {     // the three fragment sets of one op by LDS-DMA: 37.5 x 1 KiB wave-instructions
-        for (int i = wave; i < 25; i += OPL16_THREADS / 64) {
-            const int e = i * 128 + lane * 2;
-            const double *g = (e < PFRAG) ? (op.pl ? op.pl : op.pr) + e : (op.pr ? op.pr : op.pl) + (e - PFRAG);
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)g, (__attribute__((address_space(3))) void *)(dst + i * 128), 16, 0, 0);
-        }
-        const int lk = op.flags & 3, rk = (op.flags >> 2) & 3;
-        const double *inner = (lk == SK_PITCH) ? op.l.f : (rk == SK_PITCH) ? op.r.f : nullptr;
-        if (inner == nullptr) return;
-        for (int i = wave; i < 13; i += OPL16_THREADS / 64) {
-            const int e = i * 128 + lane * 2;
-            if (e < PFRAG) __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)(inner + e), (__attribute__((address_space(3))) void *)(dst + 2 * PFRAG + i * 128), 16, 0, 0);
-        }
-    };
-    for (int i = tid; i < TIPTAB; i += OPL16_THREADS) sT[i] = (unsigned char)((code_mask(i / NS) >> (i % NS)) & 1u);
-    stage(ops[run.op_begin], sP);
-    __syncthreads();
-    for (int oi = run.op_begin; oi < run.op_end; ++oi) {
-        const NvOp &op = ops[oi];
-        const int par = (oi - run.op_begin) & 1;
-        const double *buf = sP + par * PARITY_STRIDE;
-        if (oi + 1 < run.op_end) stage(ops[oi + 1], sP + (par ^ 1) * PARITY_STRIDE);
-        if (active) chunk_op1(op, buf, sT, p, lane, X, xsc);
-        __syncthreads();                                 // next fragments landed (vmcnt(0) + barrier), stores done
-    }
-}
+// the four op-list kernels
+constexpr auto k_oplist_plain = k_oplist<false, false, false>;     // formerly k_oplist<1>: no chained operand, 128 VGPRs, 4 waves per SIMD
+constexpr auto k_oplist_chain1 = k_oplist<true, false, false>;     // formerly k_oplist<9>: chained, one set of fragment regions (25.6-38.4 KB)
+constexpr auto k_oplist_score = k_oplist<true, true, false>;       // formerly k_oplist<11>: chained, double-buffered; the scoring kernel
+// formerly k_oplist<15>: the launches of the search that carry Newton tails; a kernel of its own so that the Newton code (exp, log,
+// exchange) costs the scoring kernel no register
+constexpr auto k_oplist_newton = k_oplist<true, true, true>;
 
 // ------------------------------------------------------------------------------------------
 // deterministic block reduction (fixed order: wave shuffle tree, then waves in index order)
@@ -1713,16 +1387,9 @@ void launch_eigfrags(const ModelDev *model, double *frags2, hipStream_t s) {
 void launch_eigfrags_n(const ModelDev *models, double *frags2, int n, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_eigfrags, dim3((unsigned)n), dim3(256), 0, s, models, frags2);
 }
-static int oplist_variant() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PML_OPLIST_VARIANT"); v = e ? atoi(e) : 1; }
-    return v;
-}
 static long long newton_timeout_ticks();
 static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,
                               hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
-int fused_oplist_capacity();
-bool fuse_big_genes();
 void launch_oplist(const NvOp *ops, const GeneRun *runs, int nruns, int max_mpad, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,
                    hipEvent_t start, hipEvent_t stop) {
     if (nruns <= 0) return;
@@ -1739,77 +1406,31 @@ void launch_oplist(const NvOp *ops, const GeneRun *runs, int nruns, int max_mpad
     // profiles/r03_ubench_ticket_dispatch.txt; the engine: C4 shard, 2457 workgroups on 512 slots).  Hence:
     //   bpg <= 32: one ticket partition per XCD, which keeps a gene's tiles -- and its fragment sets -- on one L2 (C3);
     //   bpg  > 32: one partition over the device (a C4 shard searches in 10.65 s against 11.0 s un-fused).
-    // PML_FUSE_BIG=0 restores the conservative rule for the second case (fused only when the whole launch is resident at once).
-    if (bpg <= 32) { launch_oplist_one(ops, runs, nruns, bpg, false, any_pitch, true, s, ctl); return; }
-    if (fuse_big_genes()) { launch_oplist_one(ops, runs, nruns, bpg, true, any_pitch, true, s, ctl); return; }
-    const int cap = fused_oplist_capacity();
-    const int genes_per_launch = std::max(1, cap / bpg);
-    for (int off = 0; off < nruns; off += genes_per_launch)
-        launch_oplist_one(ops, runs + off, std::min(genes_per_launch, nruns - off), bpg, true, any_pitch, true, s, ctl);
-}
-bool fuse_big_genes() {
-    static const bool on = !(std::getenv("PML_FUSE_BIG") && std::atoi(std::getenv("PML_FUSE_BIG")) == 0);
-    return on;
-}
-int fused_oplist_capacity() {
-    static const int cap = [] {
-        int dev = 0, cus = 256, nb = 2; hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        const size_t lds15 = (size_t)6 * PFRAG * sizeof(double) + 512;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist<15>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds15);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k_oplist<15>), 256, lds15) != hipSuccess || nb < 1) nb = 1;
-        if (nb > 2) nb = 2;                                  // 256 VGPRs: two waves per SIMD whatever the query says
-        return cus * nb;
-    }();
-    return cap;
+    launch_oplist_one(ops, runs, nruns, bpg, bpg > 32, any_pitch, true, s, ctl);
 }
 static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg_in, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,
                               hipEvent_t start, hipEvent_t stop) {
     const long long to = newton_timeout_ticks();
     const int bpg = one_part ? -bpg_in : bpg_in;
     const dim3 grid((unsigned)(one_part ? nruns * bpg_in : ((nruns + 7) / 8) * 8 * bpg_in)), block(256);
-    int v = oplist_variant();
-    if (any_pitch && (v == 2 || v == 3)) v = 1;          // pitchfork regions are not combined with double buffering
-    if (chained) {                                       // the descriptors carry OPF_CHAIN_* flags: only these variants honour them
-        static const int cv = std::getenv("PML_CHAIN_VARIANT") ? std::atoi(std::getenv("PML_CHAIN_VARIANT")) : 11;
-        v = cv == 9 ? 9 : (cv == 16 ? 16 : (cv == 10 ? 10 : 11));
-        if (ctl) v = 15;
-    }
-    if (v == 16) {                                       // one pattern per lane, 8 waves per tile (k_oplist16)
-        const size_t lds16 = (size_t)6 * PFRAG * sizeof(double) + 512;
-        static const hipError_t big16 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-        if (big16 == hipSuccess) {
-            hipExtLaunchKernelGGL(k_oplist16, grid, dim3(OPL16_THREADS), lds16, s, start, stop, 0, ops, runs, nruns, bpg_in);
-            return;
-        }
-        v = 11;
-    }
-    const bool dbuf = (v == 2 || v == 3);
-    size_t lds = (size_t)((dbuf ? 4 : 2) + (any_pitch ? 1 : 0)) * PFRAG * sizeof(double) + 512;   // 38.9 KB with pitchforks: 4 per CU
-    if (v == 11 || v == 15 || v == 10) {
-        lds = (size_t)6 * PFRAG * sizeof(double) + 512;      // 77.3 KB: two workgroups per CU, which is what its 256 VGPRs allow anyway
-        static const hipError_t big11 = [&] {
-            const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist<11>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist<15>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist<10>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            return a != hipSuccess ? a : b;
-        }();
-        if (big11 != hipSuccess && v == 11) {                // no 77 KB of dynamic LDS: the single-buffered chained variant (25.6-38.4 KB) does the same work
-            v = 9; lds = (size_t)(2 + (any_pitch ? 1 : 0)) * PFRAG * sizeof(double) + 512;
-        }
-    }
     const int ap = any_pitch ? 1 : 0;
-    switch (v) {
-        case 0: hipExtLaunchKernelGGL(k_oplist<0>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 2: hipExtLaunchKernelGGL(k_oplist<2>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 3: hipExtLaunchKernelGGL(k_oplist<3>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 5: hipExtLaunchKernelGGL(k_oplist<5>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 9: hipExtLaunchKernelGGL(k_oplist<9>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 10: hipExtLaunchKernelGGL(k_oplist<10>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 11: hipExtLaunchKernelGGL(k_oplist<11>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        case 15: hipExtLaunchKernelGGL(k_oplist<15>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
-        default: hipExtLaunchKernelGGL(k_oplist<1>, grid, block, lds, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to); break;
+    const size_t lds_single = (size_t)(2 + ap) * PFRAG * sizeof(double) + 512;     // 38.9 KB with pitchforks: 4 per CU
+    const size_t lds_double = (size_t)6 * PFRAG * sizeof(double) + 512;            // 77.3 KB: two workgroups per CU, which is what 256 VGPRs allow anyway
+    if (!chained) {                                      // only the chained kernels honour OPF_CHAIN_* flags in the descriptors
+        hipExtLaunchKernelGGL(k_oplist_plain, grid, block, lds_single, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
+        return;
     }
+    static const hipError_t big = [&] {
+        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist_score), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_double);
+        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist_newton), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_double);
+        return a != hipSuccess ? a : b;
+    }();
+    // PML_CHAIN_VARIANT=9 (tests/test_gpu_chaining.py): the single-buffered chained kernel, which also does the scoring kernel's
+    // work when 77 KB of dynamic LDS are refused
+    static const bool want_chain1 = std::getenv("PML_CHAIN_VARIANT") && std::atoi(std::getenv("PML_CHAIN_VARIANT")) == 9;
+    if (ctl) hipExtLaunchKernelGGL(k_oplist_newton, grid, block, lds_double, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
+    else if (want_chain1 || big != hipSuccess) hipExtLaunchKernelGGL(k_oplist_chain1, grid, block, lds_single, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
+    else hipExtLaunchKernelGGL(k_oplist_score, grid, block, lds_double, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
 }
 void launch_reduce(const ReduceReq *reqs, int n, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (n <= 0) return;

@@ -14,7 +14,7 @@ for _ in range(50): l = b.score()
 st = ctx.kernel_stats()["newview"]
 print("%-22s k_oplist %.4f ms/launch  lnL[0] %.6f" % (os.environ.get("TAG"), st["ms"] / st["launches"], l[0]))
 PY
-for rep in 1 2; do for a in BASE W1 W1F2 "W1 PML_CHAIN_VARIANT=10" "BASE PML_CHAIN_VARIANT=10"; do
+for rep in 1 2; do for a in BASE W1; do
   set -- $a; lib=$GRAFT_REPO_ROOT/build_ab/libpeprml_$1.so
   env TAG="$a" PEPRML_LIB=$lib $2 timeout -k 10 120 python /tmp/w1.py 2>&1 | grep k_oplist
 done; done

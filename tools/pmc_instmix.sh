@@ -11,5 +11,5 @@ for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_FLAT" "SQ_INSTS_M
   timeout -k 10 200 rocprofv3 --pmc $grp -d $O/p$i --output-format csv -- python3 $R/tools/score_loop.py 12 > $O/p$i.log 2>&1 || echo "pass $i ($grp) failed" | tee -a $O/errors.txt
   echo "pass $i done: $grp" >> $O/progress.txt
 done
-cd $R && python tools/pmc_summary.py $O "k_oplist<11>" "instruction mix, C3 chained scoring pass" > $O/summary.json; find $O -name "*.csv" -size +1M -delete; rm -rf $O/p*/*/*agent_info.csv
+cd $R && python tools/pmc_summary.py $O "k_oplist<true, true, false>" "instruction mix, C3 chained scoring pass" > $O/summary.json; find $O -name "*.csv" -size +1M -delete; rm -rf $O/p*/*/*agent_info.csv
 cat $O/summary.json | head -60; cat $O/errors.txt 2>/dev/null

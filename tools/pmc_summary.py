@@ -1,8 +1,8 @@
 """Per-launch means of every counter tools/pmc_collect.sh gathered, for the kernels whose name contains argv[2] (default
-k_oplist<11>), with the derived figures bench.py reads and the commit of the build that was measured:
+k_oplist<true, true, false>), with the derived figures bench.py reads and the commit of the build that was measured:
 python tools/pmc_summary.py OUTDIR [kernel substring] [description] > profiles/<round>_pmc_k_oplist_<leg>_<workload>.json"""
 import csv, glob, json, os, sys
-d = sys.argv[1]; pat = sys.argv[2] if len(sys.argv) > 2 else "k_oplist<11>"
+d = sys.argv[1]; pat = sys.argv[2] if len(sys.argv) > 2 else "k_oplist<true, true, false>"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 try:
     commit = open(os.path.join(root, "pepr_amd", "BUILD_COMMIT")).read().strip()
