@@ -77,12 +77,21 @@ typedef struct {
  * gene's alignment (eight sweeps of proportional counting, ambiguity codes spread over their states, floor 0.001) -- a
  * per-gene eigen-system.  Built for score / optimize / search / per-site calls and resident batches; the jackknife's
  * device-gathered replicates refuse it. */
-enum { PML_PI_RAXML_3DP = 0, PML_PI_WAG_FULL = 1, PML_PI_EMPIRICAL = 2 };
+enum { PML_PI_RAXML_3DP = 0, PML_PI_WAG_FULL = 1, PML_PI_EMPIRICAL = 2,
+       /* RAxML's PROTGAMMAGTR: the 189 free exchangeabilities of the gene are estimated by maximum likelihood (the 190th is
+        * fixed at 1), frequencies empirical.  The optimising calls (pml_optimize*, pml_search*, pml_batch_optimize,
+        * pml_batch_search, pml_model_eval) estimate them; a call that does not optimise scores a gene whose matrix was never
+        * set or estimated under the start matrix, WAG's exchangeabilities -- documented behaviour, not an error. */
+       PML_PI_GTR = 3,
+       /* pml_matrix_register returns codes from here on: `code` (even) = the registered matrix with its own frequencies, one
+        * shared model; `code + 1` = its exchangeabilities with each gene's empirical frequencies (RAxML's "F" variant). */
+       PML_PI_REGISTERED = 16 };
 
 typedef struct {
     int ncat;                /* Gamma categories (4 = RAxML PROTGAMMA; 1 = no rate heterogeneity) */
     double alpha;            /* Gamma shape (start value when optimised) */
-    int pi_mode;             /* PML_PI_RAXML_3DP (RAxML 7.2.5 PROTGAMMAWAG), PML_PI_WAG_FULL (FastTree_WAG) or PML_PI_EMPIRICAL (PROTGAMMAWAGF) */
+    int pi_mode;             /* the model: PML_PI_RAXML_3DP (RAxML 7.2.5 PROTGAMMAWAG), PML_PI_WAG_FULL (FastTree_WAG), PML_PI_EMPIRICAL
+                              * (PROTGAMMAWAGF), PML_PI_GTR (PROTGAMMAGTR) or a code of pml_matrix_register */
 } pml_model;
 
 typedef struct {
@@ -140,6 +149,23 @@ int pml_search_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char 
                      const pml_model *model, const pml_search_opts *opts, pml_result *out);
 void pml_result_free(pml_result *r);
 
+/* Models beyond WAG.  A rate matrix is 190 exchangeabilities -- the lower triangle by rows, (1,0), (2,0), (2,1), (3,0) ... in
+ * the state order ARNDCQEGHILKMFPSTWYV -- and 20 frequencies: the layout of PAML's .dat files.
+ * pml_matrix_parse_paml (host only) reads such a file's text; whatever follows the 210th number is ignored; fewer numbers, a
+ * negative or a non-finite one: PML_EPARSE.
+ * pml_matrix_register stores a matrix on the context and returns its model code (see PML_PI_REGISTERED); the frequencies
+ * are normalised to sum 1.  Registering a name again replaces nothing, it returns a new code.  Thread-safe like every
+ * context call.  Codes are accepted wherever PML_PI_EMPIRICAL is; pml_jackknife takes the own-frequency codes only and
+ * refuses "F" codes and PML_PI_GTR at entry.
+ * pml_model_eval is the reference's -matrix_eval loop (PhylogenomicPipeline2.java:1390-1452, getTreeScore :1482-1500) as ONE
+ * device batch: the tree is optimised (branch lengths, alpha if opts says so, rates where the code is PML_PI_GTR) under each
+ * of the nmodels codes; out[i] is what pml_optimize returns under codes[i] (4 categories, start alpha 1), bit for bit;
+ * *best_out (optional) = index of the highest lnL, the first one of equals. */
+int pml_matrix_parse_paml(const char *text, double *exch190, double *pi20);
+int pml_matrix_register(pml_ctx *ctx, const char *name, const double *exch190, const double *pi20, int *code_out);
+int pml_model_eval(pml_ctx *ctx, const pml_alignment *aln, const char *newick, int nmodels, const int *codes,
+                   const pml_search_opts *opts, pml_result *out, int *best_out);
+
 /* resident batches: encode + upload once, then evaluate repeatedly with inputs in HBM */
 int  pml_batch_create(pml_ctx *ctx, int n, const pml_alignment *alns, const char *const *newicks,
                       const pml_model *model, pml_batch **out);
@@ -153,6 +179,11 @@ int  pml_batch_score(pml_batch *b, double *lnl_out /* n */);
 int  pml_batch_score_stored(pml_batch *b, double *lnl_out /* n */);
 int  pml_batch_site_lnl(pml_batch *b, int gene, double *site_lnl /* nsites */);
 int  pml_batch_set_alpha(pml_batch *b, int gene /* -1 = all */, double alpha);
+/* the rate matrix of one gene (or of all: gene -1) of a resident batch.  set: any batch becomes a batch of per-gene models;
+ * pi20 NULL keeps the gene's frequencies.  get: what the gene is scored with -- the estimates after an optimisation under
+ * PML_PI_GTR, the counted frequencies of an "F" variant; frequencies sum to 1 */
+int  pml_batch_set_matrix(pml_batch *b, int gene /* -1 = all */, const double *exch190, const double *pi20 /* NULL = keep */);
+int  pml_batch_get_matrix(pml_batch *b, int gene, double *exch190_out, double *pi20_out);
 int  pml_batch_optimize(pml_batch *b, const pml_search_opts *opts, double *lnl_out, double *alpha_out);
 int  pml_batch_search(pml_batch *b, const pml_search_opts *opts, double *lnl_out, double *alpha_out);
 int  pml_batch_newick(pml_batch *b, int gene, int digits, char **out /* free with pml_free */);
@@ -200,6 +231,11 @@ int pml_jackknife_draw(int ngenes, int reps, int subset_size, unsigned long long
  * names_out = the sorted taxon union, one per line.  The three buffers are released with pml_free. */
 int pml_debug_gather(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nsel, const int *sel, int *ntax_out,
                      int *npat_out, int *mpad_out, unsigned char **codes_out, double **weights_out, char **names_out);
+/* test door of the model-build kernel (k_model): the eigen-systems of n rate matrices (n x 190 exchangeabilities, n x 20
+ * frequencies) as the device structs, sizeof(ModelDev) / 8 = 1240 doubles each: eval[20], U[20][20] (P(t) = U diag(exp(eval t))
+ * Uinv), Uinv[20][20], pi[20], Uinv transposed [20][20] */
+int pml_debug_model_build(pml_ctx *ctx, int n, const double *exch /* n x 190 */, const double *pi /* n x 20 */,
+                          double *modeldev_out /* n x 1240 */);
 /* host-only: the refinement loop's support queries on a rooted Newick with support labels (")95:0.1" or
  * ":0.1[95]"; missing = 100, fractions are x100) -- PhylogeneticTreeRefiner.java:298-359 getNextIndexToRefine,
  * AdvancedTree.java:1061-1098 getMeanDescendantSupportValues.  *ingroup_out = comma-joined sorted leaf names of
@@ -265,7 +301,8 @@ int pml_debug_fpenv(unsigned *values, int cap);
 /* profiling: HIP-event time of device kernels since the last reset (cfg.profile = 1) */
 enum { PML_K_PMAT = 0, PML_K_NEWVIEW = 1, PML_K_EVALUATE = 2, PML_K_SUMTABLE = 3, PML_K_NEWTON = 4,
        PML_K_REDUCE = 5,
-       PML_K_HOST_BUILD = 6 /* CPU ms building descriptors */, PML_K_HOST_WAIT = 7 /* CPU ms in stream sync */, PML_K_COUNT = 8 };
+       PML_K_HOST_BUILD = 6 /* CPU ms building descriptors */, PML_K_HOST_WAIT = 7 /* CPU ms in stream sync */,
+       PML_K_MODEL = 8 /* model builds (k_model): eigen-systems of per-gene and registered rate matrices */, PML_K_COUNT = 9 };
 int pml_kernel_stats(pml_ctx *ctx, int kernel, long long *launches, double *total_ms,
                      double *algo_bytes /* algorithmic bytes moved, SURVEY 8d figures */);
 /* algorithmic flops of the launches counted by pml_kernel_stats, SURVEY 8d's per-operation figures (newview inner-inner 6480,

@@ -473,6 +473,110 @@ int pml_search_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char 
     return oneshot(ctx, OP_SEARCH, n, alns, starts, model, opts, 0, out);
 }
 
+// ---- models beyond WAG --------------------------------------------------------------------
+int pml_matrix_parse_paml(const char *text, double *exch190, double *pi20) {
+    if (!text || !exch190 || !pi20) return PML_EINVAL;
+    std::string err;
+    if (!parse_paml(text, exch190, pi20, err)) { g_err = err; return PML_EPARSE; }
+    return PML_OK;
+}
+static bool matrix_ok(const double *exch, const double *pi) {
+    for (int i = 0; exch && i < NEXCH; ++i) if (!std::isfinite(exch[i]) || exch[i] < 0) return false;
+    for (int i = 0; pi && i < NS; ++i) if (!std::isfinite(pi[i]) || !(pi[i] > 0)) return false;
+    return true;
+}
+int pml_matrix_register(pml_ctx *ctx, const char *name, const double *exch190, const double *pi20, int *code_out) {
+    if (!ctx || !name || !exch190 || !pi20 || !code_out) return PML_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    if (!matrix_ok(exch190, pi20)) return ctx->c.fail(PML_EINVAL, std::string("matrix ") + name + ": exchangeabilities must be finite and >= 0, frequencies finite and > 0");
+    try {
+        Matrix m; m.name = name;
+        std::memcpy(m.exch, exch190, sizeof m.exch);
+        double sum = 0;
+        for (int i = 0; i < NS; ++i) sum += pi20[i];
+        for (int i = 0; i < NS; ++i) m.pi[i] = pi20[i] / sum;
+        ctx->c.matrices.push_back(m);
+    } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+    *code_out = PM_REGISTERED + 2 * ((int)ctx->c.matrices.size() - 1);
+    return PML_OK;
+}
+int pml_batch_set_matrix(pml_batch *b, int g, const double *exch190, const double *pi20) {
+    if (!b || !exch190 || g >= (int)b->b.genes.size()) return PML_EINVAL;
+    pml_fpguard fpg;
+    LOCKED(b);
+    if (!matrix_ok(exch190, pi20)) return b->owner->c.fail(PML_EINVAL, "set_matrix: exchangeabilities must be finite and >= 0, frequencies finite and > 0");
+    GUARD(b->b.set_matrix(g < 0 ? -1 : g, exch190, pi20));
+}
+int pml_batch_get_matrix(pml_batch *b, int g, double *exch190_out, double *pi20_out) {
+    if (!b || g < 0 || g >= (int)b->b.genes.size()) return PML_EINVAL;
+    pml_fpguard fpg;
+    LOCKED(b);
+    GUARD(b->b.get_matrix(g, exch190_out, pi20_out));
+}
+// -matrix_eval (PhylogenomicPipeline2.java:1390-1452): one tree scored under several models, the best kept.  The reference
+// starts one raxmlHPC -f e per name; here the models are the genes of ONE batch (a model code per gene, the same alignment
+// and tree in each) optimised together.  A gene's arithmetic does not depend on what shares its batch, so out[i] carries the
+// bits of pml_optimize under codes[i] with ncat 4 and start alpha 1.
+int pml_model_eval(pml_ctx *ctx, const pml_alignment *aln, const char *newick, int nmodels, const int *codes,
+                   const pml_search_opts *opts, pml_result *out, int *best_out) {
+    if (!ctx || !aln || !newick || nmodels <= 0 || !codes || !out) return PML_EINVAL;
+    pml_fpguard fpg;
+    for (int i = 0; i < nmodels; ++i) std::memset(&out[i], 0, sizeof(pml_result));
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    pml_drop_worker_caches(ctx);
+    Ctx &c = ctx->c;
+    Batch b;
+    struct Drop { Batch &b; ~Drop() { b.destroy(); } } drop{b};
+    int rc;
+    try {
+        std::vector<pml_alignment_view> views((size_t)nmodels, pml_alignment_view{aln->ntax, aln->nsites, aln->names, aln->rows});
+        std::vector<const char *> nws((size_t)nmodels, newick);
+        rc = b.create(&c, nmodels, views.data(), nws.data(), codes[0], 4, 1.0, false, codes);
+        std::vector<double> lnl((size_t)nmodels);
+        if (!rc) rc = b.optimize(opts ? opts->optimize_alpha != 0 : true, (opts && opts->epsilon > 0) ? opts->epsilon : 1e-4, lnl.data());
+        for (int i = 0; i < nmodels && !rc; ++i) {
+            const Gene &G = b.genes[i];
+            pml_result &r = out[i];
+            r.lnl = lnl[i]; r.alpha = G.alpha; r.tree_length = G.tree.length(); r.npatterns = G.aln.npat; r.nsites = G.aln.nsites;
+            r.newick = dup_string(G.tree.newick(G.aln.names, 20));
+        }
+        if (!rc && best_out) {                 // the highest lnL, the first of equals (PhylogenomicPipeline2.java:1437-1447)
+            int best = 0;
+            for (int i = 1; i < nmodels; ++i) if (lnl[i] > lnl[best]) best = i;
+            *best_out = best;
+        }
+    } catch (const std::bad_alloc &) { rc = c.fail(PML_ENOMEM, "host allocation failed"); }
+    catch (const std::exception &e) { rc = c.fail(PML_EINVAL, e.what()); }
+    for (int i = 0; i < nmodels; ++i) out[i].status = rc;
+    return rc;
+}
+// test door of k_model: n models built from n x 190 exchangeabilities and n x 20 frequencies, the ModelDev structs read back
+int pml_debug_model_build(pml_ctx *ctx, int n, const double *exch, const double *pi, double *modeldev_out) {
+    if (!ctx || n <= 0 || !exch || !pi || !modeldev_out) return PML_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    Ctx &c = ctx->c;
+    if (hipSetDevice(c.device) != hipSuccess) return c.fail(PML_EDEVICE, "hipSetDevice failed");
+    const size_t nx = (size_t)n * NEXCH * 8, np = (size_t)n * NS * 8, nm = (size_t)n * sizeof(ModelDev), nr = (size_t)n * sizeof(ModelReq);
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, nx + np + nm + nr) != hipSuccess) return c.fail(PML_ENOMEM, "device allocation failed");
+    double *dx = (double *)d, *dp = (double *)(d + nx); ModelDev *dm = (ModelDev *)(d + nx + np); ModelReq *dr = (ModelReq *)(d + nx + np + nm);
+    std::vector<ModelReq> reqs((size_t)n);
+    for (int i = 0; i < n; ++i) reqs[i] = ModelReq{dx + (size_t)i * NEXCH, dp + (size_t)i * NS, dm + i, -1, 0.0};
+    hipError_t e = hipMemcpy(dx, exch, nx, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dp, pi, np, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dr, reqs.data(), nr, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        Ctx::Ev ev = c.tic_self(K_MODEL, (double)nm);
+        launch_model_build(dr, n, c.stream, ev.a, ev.b);
+        e = hipStreamSynchronize(c.stream);
+        c.resolve_events();
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(modeldev_out, dm, nm, hipMemcpyDeviceToHost);
+    hipFree(d);
+    return e == hipSuccess ? PML_OK : c.fail(PML_EDEVICE, std::string("pml_debug_model_build: ") + hipGetErrorString(e));
+}
+
 int pml_rf_distance(const char *a, const char *b, int *rf) {
     if (!a || !b || !rf) return PML_EINVAL;
     try {

@@ -52,6 +52,7 @@ int Ctx::init_worker(const Ctx &parent) {
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = hi = 0; }
     if (hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi) != hipSuccess) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     stream2 = stream;
+    root = parent.root ? parent.root : &parent;
     return 0;
 }
 int Ctx::sync(hipStream_t s) {
@@ -68,7 +69,8 @@ void Ctx::destroy() {
     pending.clear();
     for (auto e : pool) hipEventDestroy(e);
     pool.clear();
-    for (int i = 0; i < 2; ++i) { if (d_model[i]) hipFree(d_model[i]); if (d_eigfrags[i]) hipFree(d_eigfrags[i]); d_model[i] = nullptr; d_eigfrags[i] = nullptr; }
+    for (auto &m : shared) { hipFree(m.d_model); hipFree(m.d_eigfrags); }
+    shared.clear();
     if (arena_cache) hipFree(arena_cache);
     arena_cache = nullptr; arena_cache_bytes = 0;
     if (stream && owns_stream) hipStreamDestroy(stream);
@@ -82,38 +84,188 @@ static void fill_model_dev(const Model &m, ModelDev &h) {
     std::memcpy(h.pi, m.pi, sizeof h.pi);
     for (int k = 0; k < NS; ++k) for (int j = 0; j < NS; ++j) h.UinvT[j * NS + k] = m.Uinv[k * NS + j];
 }
-// PROTGAMMAWAGF (pi_mode 2): empirical frequencies per gene (host.cpp empirical_freqs), WAG exchangeabilities, one
-// eigen-decomposition per gene on the host (20 x 20 Jacobi), models + eigen-basis fragment sets uploaded once per batch
-int Batch::build_gene_models() {
-    const size_t n = genes.size();
-    std::vector<ModelDev> h(n);
-    for (size_t g = 0; g < n; ++g) {
-        double pi[20];
-        empirical_freqs(genes[g].aln, pi);
-        Model m; m.init_pi(pi);
-        fill_model_dev(m, h[g]);
-    }
-    HIPCHK(hipMalloc((void **)&d_gmodel, n * sizeof(ModelDev)));
-    HIPCHK(hipMalloc((void **)&d_geig, n * 2 * PFRAG * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(d_gmodel, h.data(), n * sizeof(ModelDev), hipMemcpyHostToDevice, ctx->stream));
-    launch_eigfrags_n(d_gmodel, d_geig, (int)n, ctx->stream);
-    if (int rc = ctx->sync(ctx->stream)) return rc;      // h goes out of scope
-    return 0;
+const Matrix *Ctx::matrix_of(int pm) const {
+    const Ctx &r = root ? *root : *this;
+    if (pm < PM_REGISTERED || (size_t)(pm - PM_REGISTERED) / 2 >= r.matrices.size()) return nullptr;
+    return &r.matrices[(size_t)(pm - PM_REGISTERED) / 2];
 }
+std::string Ctx::model_name(int pm) const {
+    if (pm == 0) return "PROTGAMMAWAG";
+    if (pm == 1) return "PROTGAMMAWAG (full-precision frequencies)";
+    if (pm == 2) return "PROTGAMMAWAGF";
+    if (pm == PM_GTR) return "PROTGAMMAGTR";
+    const Matrix *m = matrix_of(pm);
+    if (!m) return "model code " + std::to_string(pm);
+    std::string n = "PROTGAMMA";
+    for (char ch : m->name) n += (char)std::toupper((unsigned char)ch);
+    return (pm & 1) ? n + "F" : n;
+}
+// One eigen-system per shared code and context.  The built-in WAG codes are decomposed on the host (the bits they always
+// had); a registered matrix goes through k_model like every other model that is not built in.
 int Ctx::ensure_model(int pm) {
     Ctx *ctx = this;
-    if (pm == 2) return 0;                  // PROTGAMMAWAGF: per-gene models live in the batch (Batch::build_gene_models)
-    if (pm < 0 || pm > 2) return fail(-1, "bad pi_mode");
-    if (model_ready[pm]) return 0;
-    model[pm].init(pm);
-    ModelDev h;
-    fill_model_dev(model[pm], h);
-    HIPCHK(hipMalloc(&d_model[pm], sizeof(ModelDev)));
-    HIPCHK(hipMalloc(&d_eigfrags[pm], sizeof(double) * 2 * PFRAG));
-    HIPCHK(hipMemcpy(d_model[pm], &h, sizeof h, hipMemcpyHostToDevice));
-    launch_eigfrags(d_model[pm], d_eigfrags[pm], stream);
+    if (!valid_code(pm)) return fail(-1, "bad pi_mode " + std::to_string(pm) + " (not a built-in model and not a registered matrix)");
+    if (model_per_gene(pm) || shared_of(pm)) return 0;      // per-gene models live in the batch (Batch::build_gene_models)
+    Shared sh{pm, nullptr, nullptr};
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipMalloc((void **)&sh.d_model, sizeof(ModelDev)));
+    HIPCHK(hipMalloc((void **)&sh.d_eigfrags, sizeof(double) * 2 * PFRAG));
+    if (const Matrix *M = matrix_of(pm)) {
+        struct In { double exch[NEXCH], pi[NS]; ModelReq req; } h, *d = nullptr;
+        std::memcpy(h.exch, M->exch, sizeof h.exch); std::memcpy(h.pi, M->pi, sizeof h.pi);
+        HIPCHK(hipMalloc((void **)&d, sizeof(In)));
+        h.req = ModelReq{d->exch, d->pi, sh.d_model, -1, 0.0};
+        HIPCHK(hipMemcpy(d, &h, sizeof h, hipMemcpyHostToDevice));
+        Ev ev = tic_self(K_MODEL, sizeof(ModelDev));
+        launch_model_build(&d->req, 1, stream, ev.a, ev.b);
+        if (int rc = sync(stream)) return rc;
+        HIPCHK(hipFree(d));
+    } else {
+        Model m; m.init(pm);
+        ModelDev h;
+        fill_model_dev(m, h);
+        HIPCHK(hipMemcpy(sh.d_model, &h, sizeof h, hipMemcpyHostToDevice));
+    }
+    launch_eigfrags(sh.d_model, sh.d_eigfrags, stream);
     if (int rc = sync(stream)) return rc;
-    model_ready[pm] = true;
+    HIPCHK(hipGetLastError());
+    shared.push_back(sh);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// per-gene models
+// ------------------------------------------------------------------------------------------
+int Batch::alloc_gene_models() {
+    const size_t n = genes.size();
+    HIPCHK(hipMalloc((void **)&d_gmodel, n * sizeof(ModelDev)));
+    HIPCHK(hipMalloc((void **)&d_geig, n * 2 * PFRAG * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&d_gexch, n * NEXCH * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&d_gpi, n * NS * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&d_mreq, n * sizeof(ModelReq)));
+    HIPCHK(hipHostMalloc((void **)&h_gexch, n * NEXCH * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&h_gpi, n * NS * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&h_mreq, n * sizeof(ModelReq), hipHostMallocDefault));
+    return 0;
+}
+void Batch::matrix_for(int g, double *exch, double *pi) const {
+    const int code = genes[g].model_code;
+    const Matrix *M = ctx->matrix_of(code);
+    std::memcpy(exch, M ? M->exch : wag_exch(), sizeof(double) * NEXCH);
+    // GTR starts from WAG in the scale the estimates are reported in: the last exchangeability, which stays fixed, is 1
+    if (code == PM_GTR) { const double last = exch[NEXCH - 1]; for (int i = 0; i < NEXCH; ++i) exch[i] /= last; }
+    if (model_per_gene(code)) empirical_freqs(genes[g].aln, pi);
+    else std::memcpy(pi, M ? M->pi : wag_pi(code), sizeof(double) * NS);
+    double sum = 0;
+    for (int i = 0; i < NS; ++i) sum += pi[i];
+    for (int i = 0; i < NS; ++i) pi[i] /= sum;
+}
+// Every gene gets its own ModelDev and eigen-basis fragment sets.  A gene of a shared code receives a copy of the context's
+// model (the same bytes, hence the same results as in a shared-model batch); PROTGAMMAWAGF (code 2) is decomposed on the
+// host as it always was; every other per-gene code (registered "F" variants, GTR from its WAG start) is built by k_model.
+int Batch::build_gene_models() {
+    const int n = (int)genes.size();
+    if (int rc = alloc_gene_models()) return rc;
+    std::vector<ModelDev> h(n);
+    std::vector<int> dev;
+    for (int g = 0; g < n; ++g) {
+        const int code = genes[g].model_code;
+        if (code == 2) {
+            double pi[NS];
+            empirical_freqs(genes[g].aln, pi);
+            Model m; m.init_pi(pi);
+            fill_model_dev(m, h[g]);
+            std::memcpy(h_gexch + (size_t)g * NEXCH, wag_exch(), sizeof(double) * NEXCH); std::memcpy(h_gpi + (size_t)g * NS, m.pi, sizeof m.pi);
+            HIPCHK(hipMemcpyAsync(d_gmodel + g, &h[g], sizeof(ModelDev), hipMemcpyHostToDevice, ctx->stream));
+            continue;
+        }
+        matrix_for(g, h_gexch + (size_t)g * NEXCH, h_gpi + (size_t)g * NS);
+        if (model_per_gene(code)) { dev.push_back(g); continue; }
+        if (int rc = ctx->ensure_model(code)) return rc;
+        HIPCHK(hipMemcpyAsync(d_gmodel + g, ctx->shared_of(code)->d_model, sizeof(ModelDev), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    HIPCHK(hipMemcpyAsync(d_gexch, h_gexch, (size_t)n * NEXCH * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_gpi, h_gpi, (size_t)n * NS * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = build_models(dev, -1, nullptr)) return rc;          // ends with the fragment sets of ALL genes
+    if (dev.empty()) launch_eigfrags_n(d_gmodel, d_geig, n, ctx->stream);
+    if (int rc = ctx->sync(ctx->stream)) return rc;      // h goes out of scope
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// h_mreq is reused by the next call: every caller synchronises the stream (a score, or explicitly) before it calls again.
+// PML_MODEL_HOST=1 is the A/B arm this kernel is judged against: the same models decomposed one after the
+// other on the host (Model::init) and uploaded.
+int Batch::build_models(const std::vector<int> &gs, int patch, const double *vals) {
+    if (gs.empty()) return 0;
+    static const bool host_arm = std::getenv("PML_MODEL_HOST") != nullptr;
+    const int n = (int)genes.size(), m = (int)gs.size();
+    if (host_arm) {
+        if (!h_gmodel) HIPCHK(hipHostMalloc((void **)&h_gmodel, (size_t)n * sizeof(ModelDev), hipHostMallocDefault));
+        for (int i = 0; i < m; ++i) {
+            const int g = gs[i];
+            double ex[NEXCH];
+            std::memcpy(ex, h_gexch + (size_t)g * NEXCH, sizeof ex);
+            if (patch >= 0) ex[patch] = vals[i];
+            Model md; md.init(ex, h_gpi + (size_t)g * NS);
+            fill_model_dev(md, h_gmodel[g]);
+            HIPCHK(hipMemcpyAsync(d_gmodel + g, h_gmodel + g, sizeof(ModelDev), hipMemcpyHostToDevice, ctx->stream));
+        }
+    } else {
+        for (int i = 0; i < m; ++i) {
+            const int g = gs[i];
+            h_mreq[i] = ModelReq{d_gexch + (size_t)g * NEXCH, d_gpi + (size_t)g * NS, d_gmodel + g, patch, patch >= 0 ? vals[i] : 0.0};
+        }
+        HIPCHK(hipMemcpyAsync(d_mreq, h_mreq, (size_t)m * sizeof(ModelReq), hipMemcpyHostToDevice, ctx->stream));
+        Ctx::Ev ev = ctx->tic_self(K_MODEL, (double)m * sizeof(ModelDev));
+        launch_model_build(d_mreq, m, ctx->stream, ev.a, ev.b);
+    }
+    launch_eigfrags_n(d_gmodel, d_geig, n, ctx->stream);
+    return 0;
+}
+// A model change counts as a move of every branch of the gene: its cached CLVs are invalid, and a recorded scoring plan
+// recomputes all its transition matrices from the rebuilt ModelDev at the next replay (k_pmat reads the model through the
+// request's pointer on every replay).  A batch created with a shared model becomes a per-gene batch here: every gene gets a
+// copy of the shared model first, and a recorded plan -- whose requests name no model -- is dropped.
+int Batch::set_matrix(int g, const double *exch, const double *pi) {
+    const int n = (int)genes.size();
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!d_gmodel) {
+        if (int rc = alloc_gene_models()) return rc;
+        for (int i = 0; i < n; ++i) {
+            matrix_for(i, h_gexch + (size_t)i * NEXCH, h_gpi + (size_t)i * NS);
+            HIPCHK(hipMemcpyAsync(d_gmodel + i, d_shared, sizeof(ModelDev), hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(d_geig + (size_t)i * 2 * PFRAG, d_shared_eig, sizeof(double) * 2 * PFRAG, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        plan.valid = false;
+    }
+    std::vector<int> gs;
+    for (int i = 0; i < n; ++i) if (g < 0 || i == g) gs.push_back(i);
+    for (int i : gs) {
+        std::memcpy(h_gexch + (size_t)i * NEXCH, exch, sizeof(double) * NEXCH);
+        if (pi) {
+            double sum = 0;
+            for (int k = 0; k < NS; ++k) sum += pi[k];
+            for (int k = 0; k < NS; ++k) h_gpi[(size_t)i * NS + k] = pi[k] / sum;
+        }
+        invalidate_all(i);
+    }
+    HIPCHK(hipMemcpyAsync(d_gexch, h_gexch, (size_t)n * NEXCH * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_gpi, h_gpi, (size_t)n * NS * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = build_models(gs, -1, nullptr)) return rc;
+    if (int rc = ctx->sync(ctx->stream)) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int Batch::get_matrix(int g, double *exch, double *pi) const {
+    if (h_gexch) {
+        if (exch) std::memcpy(exch, h_gexch + (size_t)g * NEXCH, sizeof(double) * NEXCH);
+        if (pi) std::memcpy(pi, h_gpi + (size_t)g * NS, sizeof(double) * NS);
+        return 0;
+    }
+    double ex[NEXCH], p[NS];
+    matrix_for(g, ex, p);
+    if (exch) std::memcpy(exch, ex, sizeof ex);
+    if (pi) std::memcpy(pi, p, sizeof p);
     return 0;
 }
 hipEvent_t Ctx::get_event() {
@@ -181,16 +333,20 @@ static std::atomic<int> g_batch_id{0};
 static double now_ms();
 
 int Batch::create(Ctx *c, int n, const pml_alignment_view *alns, const char *const *newicks, int pm, int nc,
-                  double alpha, bool score_only) {
+                  double alpha, bool score_only, const int *gene_codes) {
     ctx = c; pi_mode = pm; ncat = nc; score_only_batch = score_only;
     det_id = ++g_batch_id;
     virtual_cherries = std::getenv("PML_NO_CHERRY") == nullptr;
     virtual_pitch = virtual_cherries && std::getenv("PML_NO_PITCH") == nullptr;
     if (n <= 0) return ctx->fail(-1, "empty batch");
     if (nc != 1 && nc != 4) return ctx->fail(-1, "ncat must be 1 or 4");
-    if (int rc = ctx->ensure_model(pm)) return rc;
+    if (gene_codes) { for (int g = 0; g < n; ++g) if (!ctx->valid_code(gene_codes[g])) return ctx->fail(-1, "bad pi_mode " + std::to_string(gene_codes[g])); }
+    else if (int rc = ctx->ensure_model(pm)) return rc;
+    const bool per_gene = gene_codes != nullptr || model_per_gene(pm);
+    if (!per_gene) { d_shared = ctx->shared_of(pm)->d_model; d_shared_eig = ctx->shared_of(pm)->d_eigfrags; }
     HIPCHK(hipSetDevice(ctx->device));
     genes.resize(n);
+    for (int g = 0; g < n; ++g) genes[g].model_code = gene_codes ? gene_codes[g] : pm;
     const double t_create0 = now_ms();
     {   // encode / parse / NJ are independent per gene: host threads (plain std::thread, no GPU work)
         const int nthreads = std::max(1, std::min({n, 16, (int)std::thread::hardware_concurrency()}));
@@ -214,7 +370,7 @@ int Batch::create(Ctx *c, int n, const pml_alignment_view *alns, const char *con
     }
     if (std::getenv("PML_TRACE")) fprintf(stderr, "[pml] create: encode + start trees of %d genes %.1f ms\n", n, now_ms() - t_create0);
     if (int rc = layout(alpha, score_only)) return rc;
-    return pm == 2 ? build_gene_models() : 0;
+    return per_gene ? build_gene_models() : 0;
 }
 
 // device arena + per-gene pointers from (ntax, mpad) alone; host-encoded codes/weights are uploaded when present
@@ -313,6 +469,13 @@ void Batch::destroy() {
     }
     if (d_gmodel) { hipFree(d_gmodel); d_gmodel = nullptr; }
     if (d_geig) { hipFree(d_geig); d_geig = nullptr; }
+    if (d_gexch) { hipFree(d_gexch); d_gexch = nullptr; }
+    if (d_gpi) { hipFree(d_gpi); d_gpi = nullptr; }
+    if (d_mreq) { hipFree(d_mreq); d_mreq = nullptr; }
+    if (h_gexch) { hipHostFree(h_gexch); h_gexch = nullptr; }
+    if (h_gpi) { hipHostFree(h_gpi); h_gpi = nullptr; }
+    if (h_mreq) { hipHostFree(h_mreq); h_mreq = nullptr; }
+    if (h_gmodel) { hipHostFree(h_gmodel); h_gmodel = nullptr; }
     if (ev_stagger) { hipEventDestroy(ev_stagger); ev_stagger = nullptr; }
     if (d_nsync2) hipFree(d_nsync2);
     if (d_frags2) hipFree(d_frags2);
@@ -375,8 +538,9 @@ int Batch::create_replicates(Ctx *c, const GeneStore &store, const std::vector<s
     virtual_pitch = virtual_cherries && std::getenv("PML_NO_PITCH") == nullptr;
     const int n = (int)sel.size();
     if (n <= 0) return ctx->fail(-1, "empty batch");
-    if (pm == 2) return ctx->fail(-1, "PROTGAMMAWAGF (empirical frequencies) is built for score / optimize / search calls, not for device-gathered replicates");
+    if (model_per_gene(pm)) return ctx->fail(-1, ctx->model_name(pm) + " (a model per gene: empirical frequencies or estimated rates) is built for score / optimize / search calls, not for device-gathered replicates");
     if (int rc = ctx->ensure_model(pm)) return rc;
+    d_shared = ctx->shared_of(pm)->d_model; d_shared_eig = ctx->shared_of(pm)->d_eigfrags;
     HIPCHK(hipSetDevice(ctx->device));
     genes.resize(n);
     struct SegH { int rep, gene, off; size_t rowmap_off; };
@@ -661,7 +825,7 @@ int Batch::flush_deferred() {
     const size_t lo = deferred.front().base, hi = deferred.back().base + deferred.back().bytes;
     const hipStream_t cs = deferred.front().lane ? ctx->stream2 : ctx->stream;
     HIPCHK(hipMemcpyAsync((char *)d_stage + lo, (char *)h_stage + lo, hi - lo, hipMemcpyHostToDevice, cs));
-    const ModelDev *md = pi_mode < 2 ? ctx->d_model[pi_mode] : nullptr;      // per-gene models travel in the requests
+    const ModelDev *md = d_gmodel ? nullptr : d_shared;      // per-gene models travel in the requests
     static const bool serialize = std::getenv("PML_SERIALIZE") != nullptr;      // diagnostic: a host sync after every launch
 #define PML_SER() do { if (serialize) hipStreamSynchronize(st); } while (0)
     if (serialize) hipStreamSynchronize(cs);
@@ -1192,7 +1356,7 @@ int Batch::replay_plan(double *lnl) {
     }
     char *ds = (char *)P.d;
     if (changed) HIPCHK(hipMemcpyAsync(ds + P.o_req, hreq, P.nreq * sizeof(PmatReq), hipMemcpyHostToDevice, ctx->stream));
-    const ModelDev *md = pi_mode < 2 ? ctx->d_model[pi_mode] : nullptr;      // per-gene models travel in the requests
+    const ModelDev *md = d_gmodel ? nullptr : d_shared;      // per-gene models travel in the requests
     // the three launches carry their timing events themselves (profile mode): nothing but kernels in the queue
     Ctx::Ev ev = ctx->tic_self(K_PMAT, (double)P.nreq * PFRAG * 8);
     launch_pmat(md, (const PmatReq *)(ds + P.o_req), d_frags, (int)P.nreq, ctx->stream, d_gmodel != nullptr, ev.a, ev.b);
@@ -1544,6 +1708,65 @@ int Batch::opt_alpha(const std::vector<char> &active, double *lnl, double tol) {
     return 0;
 }
 
+// PROTGAMMAGTR: one sweep over the 189 free exchangeabilities (the last of the 190 stays 1: a common factor of all rates
+// cancels in the normalisation to one substitution per site) of every active GTR gene.  Rate k of all genes is optimised
+// in lock step by Brent on log(rate), the window logic of opt_alpha (+-ln 4 around the current value, doubled and continued
+// while the minimum sits on a window edge that is not a global bound).  One trial = k_model for the active genes with rate k
+// patched (nothing is uploaded but the requests) -> k_eigfrags -> the scoring step; the host reads the lnL and nothing else.
+// The accepted value is written to the device copy of the gene's exchangeabilities before the next rate starts.
+int Batch::opt_rates(const std::vector<char> &active, double *lnl, double tol) {
+    const int n = (int)genes.size();
+    std::vector<char> gtr(n, 0);
+    std::vector<int> all;
+    for (int g = 0; g < n; ++g) if (active[g] && genes[g].model_code == PM_GTR) { gtr[g] = 1; all.push_back(g); }
+    if (all.empty()) return 0;
+    const double t0 = now_ms(); const long trials0 = cnt_rate_trials;
+    const double LMIN = std::log(RATE_MIN), LMAX = std::log(RATE_MAX);
+    std::vector<double> f(n), fu(n), vals; std::vector<int> gs;
+    if (int rc = score(gtr, fu.data())) return rc;
+    for (int g : all) f[g] = -fu[g];
+    std::vector<Brent> br(n);
+    std::vector<double> W(n), lo(n), hi(n);
+    std::vector<int> win(n);
+    for (int k = 0; k < NEXCH - 1; ++k) {
+        std::vector<char> act(gtr);
+        auto open_window = [&](int g, double x, double fx) {
+            lo[g] = std::max(LMIN, x - W[g]); hi[g] = std::min(LMAX, x + W[g]);
+            br[g].start(lo[g], hi[g], x, fx, tol);
+        };
+        for (int g : all) {
+            W[g] = std::log(4.0); win[g] = 0;
+            open_window(g, std::min(LMAX, std::max(LMIN, std::log(h_gexch[(size_t)g * NEXCH + k]))), f[g]);
+        }
+        for (;;) {
+            gs.clear(); vals.clear();
+            for (int g : all) {
+                if (!act[g]) continue;
+                for (;;) {
+                    if (br[g].propose()) { gs.push_back(g); vals.push_back(std::exp(br[g].u)); break; }
+                    const double x = br[g].x, edge = 4 * tol;
+                    if (++win[g] < 8 && ((x - lo[g] < edge && lo[g] > LMIN) || (hi[g] - x < edge && hi[g] < LMAX))) { W[g] *= 2; open_window(g, x, br[g].fx); continue; }
+                    act[g] = 0; break;
+                }
+            }
+            if (gs.empty()) break;
+            if (int rc = build_models(gs, k, vals.data())) return rc;
+            cnt_rate_trials += (long)gs.size();
+            if (int rc = score(act, fu.data())) return rc;
+            for (int g : gs) br[g].update(-fu[g]);
+        }
+        for (int g : all) { h_gexch[(size_t)g * NEXCH + k] = std::exp(br[g].x); f[g] = br[g].fx; }
+        HIPCHK(hipMemcpyAsync(d_gexch, h_gexch, (size_t)n * NEXCH * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // the models of the accepted rates (a gene's last trial is not its best one)
+    if (int rc = build_models(all, -1, nullptr)) return rc;
+    if (int rc = ctx->sync(ctx->stream)) return rc;
+    HIPCHK(hipGetLastError());
+    for (int g : all) { invalidate_all(g); lnl[g] = -f[g]; }
+    if (std::getenv("PML_TRACE")) fprintf(stderr, "[pml] rates sweep: %d genes, %ld model builds + scoring steps, %.1f ms\n", (int)all.size(), cnt_rate_trials - trials0, now_ms() - t0);
+    return 0;
+}
+
 int Batch::optimize(bool opt_alpha_flag, double eps, double *lnl, const std::vector<char> *mask) {
     const int n = (int)genes.size();
     std::vector<char> active(n, 1);
@@ -1578,6 +1801,8 @@ int Batch::optimize(bool opt_alpha_flag, double eps, double *lnl, const std::vec
             if (int rc = smooth_pass(sm, md, thr)) return rc;
             for (int g = 0; g < n; ++g) if (sm[g] && md[g] < thr) sm[g] = 0;
         }
+        // a round of a GTR gene: branch smoothing, all rates, alpha (cyclic: the order the rounds repeat is what matters)
+        if (rates_on && d_gexch) { if (int rc = opt_rates(active, nl.data(), eps >= 0.05 ? 1e-2 : 1e-3)) return rc; }
         if (opt_alpha_flag) { if (int rc = opt_alpha(active, nl.data(), eps >= 0.05 ? 1e-2 : 1e-4)) return rc; }
         else { if (int rc = evaluate(active, nl.data())) return rc; }
         for (int g = 0; g < n; ++g) {

@@ -14,7 +14,16 @@ namespace pml {
 
 constexpr int MAXTAIL = 4;            // tail requests (evaluate / sumtable+Newton) per gene per run()
 
-enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_COUNT = 8 };
+enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_COUNT = 9 };
+
+// Model codes (pml_model.pi_mode): 0 / 1 WAG with fixed frequencies, 2 WAG with the gene's empirical frequencies, 3 GTR
+// (exchangeabilities estimated per gene, empirical frequencies), 16 + 2 i the i-th registered matrix with its own
+// frequencies, 17 + 2 i its exchangeabilities with empirical frequencies.  A code is either SHARED (one eigen-system per
+// context, cached) or PER GENE (every gene of a batch carries its own ModelDev): the one predicate that decides.
+enum { PM_GTR = 3, PM_REGISTERED = 16 };
+inline bool model_per_gene(int pm) { return pm == 2 || pm == PM_GTR || (pm >= PM_REGISTERED && (pm & 1)); }
+constexpr double RATE_MIN = 1e-7, RATE_MAX = 1e6;     // bounds of an estimated exchangeability (the last of the 190 is fixed at 1)
+struct Matrix { std::string name; double exch[NEXCH]; double pi[NS]; };
 
 struct Ctx {
     int device = 0;
@@ -23,10 +32,17 @@ struct Ctx {
     hipStream_t stream2 = nullptr;      // second lane of a chained smoothing pass (half the genes each, overlapped)
     std::mutex mu;
     std::string last_error;
-    Model model[2];
-    bool model_ready[2] = {false, false};
-    ModelDev *d_model[2] = {nullptr, nullptr};
-    double *d_eigfrags[2] = {nullptr, nullptr};   // 2*PFRAG doubles each
+    // one eigen-system per SHARED model code used on this context so far: the model and its 2*PFRAG eigen-basis fragments
+    struct Shared { int code; ModelDev *d_model; double *d_eigfrags; };
+    std::vector<Shared> shared;
+    const Shared *shared_of(int pm) const { for (auto &m : shared) if (m.code == pm) return &m; return nullptr; }
+    // registered rate matrices (pml_matrix_register) live on the context the caller created; its worker contexts read them
+    // through `root` (registration and every batch creation hold the root's mutex)
+    const Ctx *root = nullptr;
+    std::vector<Matrix> matrices;
+    const Matrix *matrix_of(int pm) const;        // null: not a registered code
+    bool valid_code(int pm) const { return (pm >= 0 && pm <= PM_GTR) || matrix_of(pm) != nullptr; }
+    std::string model_name(int pm) const;         // the RAxML name of a code, for messages
     struct KStat { long long launches = 0; double ms = 0; double bytes = 0; double flops = 0; } stats[K_COUNT];
     long long newton_giveups = 0, newton_reissued = 0, newton_seq_launches = 0;   // k_newton fallback statistics (pml_newton_fallbacks)
     struct Ev { int kind; hipEvent_t a, b; };
@@ -63,6 +79,7 @@ struct Gene {
     double alpha = 1.0;
     double rates[NCAT] = {1, 1, 1, 1};
     unsigned rates_epoch = 0;      // bumped by set_alpha (cached score plans refresh a gene's rates only when it moved)
+    int model_code = 0;            // pml_model.pi_mode of this gene (pml_model_eval: one batch, a code per gene)
     // device pointers (inside the batch arena)
     uint8_t *d_codes = nullptr;
     double *d_weight = nullptr;
@@ -113,11 +130,27 @@ struct PendingOp { int gene, out_kind, out_id, level; Side child[2]; double t[2]
 struct Batch {
     Ctx *ctx = nullptr;
     int pi_mode = 0, ncat = 4, det_id = 0;
-    // pi_mode 2 (PROTGAMMAWAGF): every gene has its own eigen-system from its empirical frequencies
+    const ModelDev *d_shared = nullptr; const double *d_shared_eig = nullptr;      // the context's model of a shared code
+    // per-gene models (model_per_gene codes, genes of different codes, or after set_matrix): every gene has its own eigen-system
     ModelDev *d_gmodel = nullptr; double *d_geig = nullptr;       // [genes] models, [genes][2*PFRAG] eigen-basis fragment sets
-    const ModelDev *model_of(int g) const { return d_gmodel ? d_gmodel + g : ctx->d_model[pi_mode]; }
-    const double *eig_of(int g) const { return d_geig ? d_geig + (size_t)g * 2 * PFRAG : ctx->d_eigfrags[pi_mode]; }
+    // what the genes' models are built from, device copies read by k_model and pinned host mirrors: [genes][190], [genes][20]
+    double *d_gexch = nullptr, *d_gpi = nullptr, *h_gexch = nullptr, *h_gpi = nullptr;
+    ModelReq *d_mreq = nullptr, *h_mreq = nullptr;                // [genes] build requests
+    ModelDev *h_gmodel = nullptr;                                 // [genes], PML_MODEL_HOST=1 only: the host-built A/B arm of build_models
+    const ModelDev *model_of(int g) const { return d_gmodel ? d_gmodel + g : d_shared; }
+    const double *eig_of(int g) const { return d_geig ? d_geig + (size_t)g * 2 * PFRAG : d_shared_eig; }
+    int alloc_gene_models();
     int build_gene_models();
+    // the exchangeabilities and (normalised) frequencies gene g's code stands for (empirical frequencies counted from its alignment)
+    void matrix_for(int g, double *exch190, double *pi20) const;
+    // k_model + k_eigfrags for the listed genes from d_gexch / d_gpi; patch >= 0: rate `patch` of gene gs[i] counts as vals[i]
+    int build_models(const std::vector<int> &gs, int patch, const double *vals);
+    int set_matrix(int g /* -1 = all */, const double *exch190, const double *pi20 /* null = keep */);
+    int get_matrix(int g, double *exch190, double *pi20) const;
+    // PROTGAMMAGTR: one sweep over the 189 free rates of every active GTR gene, each by Brent on its logarithm, genes in lock step
+    int opt_rates(const std::vector<char> &active, double *lnl, double tol);
+    bool rates_on = true;          // optimize() estimates the rates of GTR genes (a search holds them fixed between its first and last optimisation)
+    long cnt_rate_trials = 0;
     int share = 1;                 // batches working on the device at the same time (groups of one search call): free HBM is divided by it
     double newton_tol = 1e-8;      // Newton stop |dt| < tol: 1e-8 fine, 1e-6 in coarse phases
     std::vector<Gene> genes;
@@ -191,7 +224,7 @@ struct Batch {
     int chain_sync();                  // wait for everything enqueued; the staging buffer is free again
 
     int create(Ctx *c, int n, const pml_alignment_view *alns, const char *const *newicks,
-               int pi_mode, int ncat, double alpha, bool score_only);
+               int pi_mode, int ncat, double alpha, bool score_only, const int *gene_codes = nullptr /* a code per gene instead of pi_mode */);
     // one batch gene per replicate = the concatenation of the selected store genes (sorted taxon union, absent
     // taxa = gap rows, MSAConcatenator rules); code matrices are gathered on the device, NJ start trees come from
     // the summed pair counts: no column text is touched again

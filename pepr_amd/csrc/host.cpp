@@ -71,11 +71,14 @@ static void sym_eig20(std::vector<double> &A, double *eval, std::vector<double> 
     V.swap(V2);
 }
 
+const double *wag_exch() { return kWagLower; }
+const double *wag_pi(int pi_mode) { return pi_mode == 1 ? kWagPiFull : kWagPi3dp; }
 void Model::init(int pi_mode) { init_pi(pi_mode == 1 ? kWagPiFull : kWagPi3dp); }
-void Model::init_pi(const double *pi20) {
+void Model::init_pi(const double *pi20) { init(kWagLower, pi20); }      // WAG is the built-in instance
+void Model::init(const double *exch190, const double *pi20) {
     double S[400] = {0};
     int k = 0;
-    for (int i = 1; i < 20; ++i) for (int j = 0; j < i; ++j) { S[i * 20 + j] = S[j * 20 + i] = kWagLower[k++]; }
+    for (int i = 1; i < 20; ++i) for (int j = 0; j < i; ++j) { S[i * 20 + j] = S[j * 20 + i] = exch190[k++]; }
     double sum = 0;
     for (int i = 0; i < 20; ++i) { pi[i] = pi20[i]; sum += pi[i]; }
     for (int i = 0; i < 20; ++i) pi[i] /= sum;
@@ -94,6 +97,22 @@ void Model::init_pi(const double *pi20) {
         U[i * 20 + j] = V[i * 20 + j] / std::sqrt(pi[i]);
         Uinv[j * 20 + i] = V[i * 20 + j] * std::sqrt(pi[i]);
     }
+}
+
+// PAML .dat layout: 190 lower-triangle exchangeabilities by rows, then 20 frequencies; whatever follows the 210th number
+// (the tables end in comment lines) is ignored
+bool parse_paml(const char *text, double *exch190, double *pi20, std::string &err) {
+    const char *p = text;
+    for (int k = 0; k < 210; ++k) {
+        while (*p && std::isspace((unsigned char)*p)) ++p;
+        char *end = nullptr;
+        const double v = *p ? std::strtod(p, &end) : 0.0;
+        if (!*p || end == p) { err = "rate matrix: " + std::to_string(k) + " numbers found, 210 expected (190 exchangeabilities, 20 frequencies)"; return false; }
+        if (!std::isfinite(v) || v < 0) { err = "rate matrix: number " + std::to_string(k + 1) + " is negative or not finite"; return false; }
+        (k < 190 ? exch190[k] : pi20[k - 190]) = v;
+        p = end;
+    }
+    return true;
 }
 
 // regularised lower incomplete gamma P(a,x)

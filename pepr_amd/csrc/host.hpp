@@ -20,7 +20,12 @@ struct Model {
     double Uinv[400];
     void init(int pi_mode);
     void init_pi(const double *pi20);    // WAG exchangeabilities with the given frequencies (PROTGAMMAWAGF)
+    // any reversible matrix: 190 exchangeabilities (lower triangle by rows, ARNDCQEGHILKMFPSTWYV) and 20 frequencies
+    void init(const double *exch190, const double *pi20);
 };
+const double *wag_exch();                // the built-in 190 exchangeabilities
+const double *wag_pi(int pi_mode);       // and the frequencies Model::init(pi_mode) uses (not normalised)
+bool parse_paml(const char *text, double *exch190, double *pi20, std::string &err);
 struct EncodedAlignment;
 // empirical amino-acid frequencies, RAxML's "F" models (spec: oracle/pml_oracle.c po_empirical_freqs)
 void empirical_freqs(const EncodedAlignment &a, double *pi20);

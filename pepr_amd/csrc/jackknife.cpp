@@ -133,6 +133,12 @@ extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *gene
     const int sworld = (opts && opts->shard_world > 1) ? opts->shard_world : 1, srank = sworld > 1 ? opts->shard_rank : 0;
     if (srank < 0 || srank >= sworld) return PML_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->c.mu);
+    // a replicate is a device-side concatenation of genes: it has no alignment text to count frequencies from and no matrix
+    // of its own, so the per-gene models are refused here, before anything is encoded or uploaded
+    if (model && !ctx->c.valid_code(model->pi_mode)) return ctx->c.fail(PML_EINVAL, "bad pi_mode " + std::to_string(model->pi_mode));
+    if (model && model_per_gene(model->pi_mode))
+        return ctx->c.fail(PML_EINVAL, ctx->c.model_name(model->pi_mode) + " is not available for the gene-wise jackknife: its replicates are gathered on the device and "
+                                       "carry one shared model (use PROTGAMMAWAG or a registered matrix with its own frequencies)");
     pml_drop_worker_caches(ctx);
     try {
         std::vector<int> all(ngenes); for (int i = 0; i < ngenes; ++i) all[i] = i;

@@ -34,6 +34,19 @@ struct ModelDev {
     double UinvT[NS * NS];  // UinvT[j][k] = Uinv[k][j]: a column of Uinv contiguous (k_pmat reads it with scalar loads)
 };
 
+// request for one model build (k_model): the eigen-system of the reversible rate matrix with exchangeabilities `exch` (190,
+// lower triangle by rows, state order ARNDCQEGHILKMFPSTWYV) and frequencies `pi` (20, normalised by the kernel), both in HBM.
+// patch >= 0: entry `patch` of exch counts as patch_val and memory is not touched -- one trial value of one rate while the
+// exchangeabilities are being estimated (PROTGAMMAGTR)
+struct ModelReq {
+    const double *exch;
+    const double *pi;
+    ModelDev *out;
+    int patch;
+    double patch_val;
+};
+constexpr int NEXCH = NS * (NS - 1) / 2;
+
 // request for one transition-matrix fragment set: P(t * rate_c), c = 0..3
 struct PmatReq {
     double t;
@@ -182,6 +195,8 @@ void launch_sh(const ShReq *reqs, int n, hipStream_t s);
 // per_request: the requests carry their own models (PmatReq::md), `model` is ignored
 void launch_pmat(const ModelDev *model, const PmatReq *reqs, double *frags, int n, hipStream_t s, bool per_request = false,
                  hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// n models built from their requests (device memory), one wavefront each; follow it with launch_eigfrags_n
+void launch_model_build(const ModelReq *reqs, int n, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // constant fragment sets for the eigen-basis transforms used by the sumtable:
 //   set 0: x_i = sum_s pi_s U[s][i] A[s]     set 1: y_i = sum_j Uinv[i][j] B[j]
 void launch_eigfrags(const ModelDev *model, double *frags2, hipStream_t s);

@@ -181,6 +181,125 @@ __global__ __launch_bounds__(256) void k_eigfrags(const ModelDev *__restrict__ m
 }
 
 // ------------------------------------------------------------------------------------------
+// k_model: the eigen-system of a reversible 20-state rate matrix from 190 exchangeabilities and 20 frequencies -- what
+// Model::init does on the host (host.cpp), for a whole batch of genes at once: while a gene's exchangeabilities are being
+// ESTIMATED (PROTGAMMAGTR) every trial value of the objective function changes every active gene's matrix.
+// One wavefront = one workgroup = one model; nothing is shared between workgroups.  B = pi^1/2 Q pi^-1/2 (symmetric) and the
+// accumulated rotations V live in LDS (2 x 3.2 KB).  Parallel-ordered Jacobi: a round-robin tournament over the 20 indices
+// gives 19 steps of 10 DISJOINT index pairs per sweep; the ten rotations of a step commute, so the wave applies them at once
+// (lane = (pair k, row group i0): 50 lanes x 4 rows) -- first to the columns of B and V, then to the rows of B -- which is
+// exactly the result of applying them one after the other as the host's cyclic sweep does.  Every lane derives the rotation
+// of its pair itself from the three entries it depends on (no broadcast step); angles in the host's stable form
+// t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), with the library's correctly rounded sqrt and division (raw v_rsq_f64 /
+// v_sqrt_f64 results are not).  A sweep starts with the off-diagonal norm, summed in a fixed order and identical in every
+// lane: below 1e-40 (the host's bound) the wave stops, after MODEL_MAX_SWEEPS it stops regardless.  Fixed order throughout:
+// the same request gives the same bits whatever else is in the launch.
+// ------------------------------------------------------------------------------------------
+constexpr int MODEL_THREADS = 64;
+constexpr int MODEL_MAX_SWEEPS = 40;
+__global__ __launch_bounds__(MODEL_THREADS) void k_model(const ModelReq *__restrict__ reqs) {
+    __shared__ double sB[NS * NS], sV[NS * NS], sPi[NS], sRt[NS], sRow[NS];
+    __shared__ int sOrd[NS];
+    const ModelReq &rq = reqs[blockIdx.x];
+    const int lane = threadIdx.x;
+    // exchangeabilities: lower triangle by rows -> symmetric S (in sV for now), the patched entry from the request
+    for (int e = lane; e < NS * (NS - 1) / 2; e += MODEL_THREADS) {
+        int i = 1;
+        while (i * (i + 1) / 2 <= e) ++i;
+        const int j = e - i * (i - 1) / 2;
+        const double v = e == rq.patch ? rq.patch_val : rq.exch[e];
+        sV[i * NS + j] = v; sV[j * NS + i] = v;
+    }
+    if (lane < NS) { sPi[lane] = rq.pi[lane]; sV[lane * (NS + 1)] = 0.0; }
+    __syncthreads();
+    double sum = 0.0;
+    for (int i = 0; i < NS; ++i) sum += sPi[i];
+    __syncthreads();
+    if (lane < NS) { const double p = sPi[lane] / sum; sPi[lane] = p; sRt[lane] = sqrt(p); }
+    __syncthreads();
+    if (lane < NS) {                              // row sums of S pi, in the host's order
+        double row = 0.0;
+        for (int j = 0; j < NS; ++j) if (j != lane) row += sV[lane * NS + j] * sPi[j];
+        sRow[lane] = row;
+    }
+    __syncthreads();
+    double mu = 0.0;                              // substitutions per site of the unscaled matrix
+    for (int i = 0; i < NS; ++i) mu += sPi[i] * sRow[i];
+    for (int e = lane; e < NS * NS; e += MODEL_THREADS) {
+        const int i = e / NS, j = e % NS;
+        const double qij = (i == j ? -sRow[i] : sV[e] * sPi[j]) / mu, qji = (i == j ? -sRow[i] : sV[e] * sPi[i]) / mu;
+        const double bij = sRt[i] * qij / sRt[j], bji = sRt[j] * qji / sRt[i];
+        sB[e] = i == j ? bij : 0.5 * (bij + bji);
+    }
+    __syncthreads();
+    for (int e = lane; e < NS * NS; e += MODEL_THREADS) sV[e] = (e / NS == e % NS) ? 1.0 : 0.0;
+    __syncthreads();
+    const int k = lane % 10, i0 = lane / 10;      // pair of the step, first of the lane's four rows (lanes 50..63 only watch)
+    for (int sweep = 0; sweep < MODEL_MAX_SWEEPS; ++sweep) {
+        if (lane < NS) {
+            double o = 0.0;
+            for (int j = lane + 1; j < NS; ++j) o += sB[lane * NS + j] * sB[lane * NS + j];
+            sRow[lane] = o;
+        }
+        __syncthreads();
+        double off = 0.0;
+        for (int i = 0; i < NS; ++i) off += sRow[i];
+        if (off < 1e-40) break;                   // the same value in every lane
+        for (int r = 0; r < NS - 1; ++r) {
+            // round r of the tournament: 19 meets r, (r + k) mod 19 meets (r - k) mod 19 for k = 1..9
+            const int a = k == 0 ? NS - 1 : (r + k) % (NS - 1), b = k == 0 ? r : (r + NS - 1 - k) % (NS - 1);
+            const int p = a < b ? a : b, q = a < b ? b : a;
+            const double app = sB[p * (NS + 1)], aqq = sB[q * (NS + 1)], apq = sB[p * NS + q];
+            double c = 1.0, s = 0.0;
+            if (fabs(apq) >= 1e-300) {
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                c = 1.0 / sqrt(t * t + 1.0); s = t * c;
+            }
+            __syncthreads();                      // every lane has read its pair's entries
+            if (lane < 50) {
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {  // columns p, q of B and V
+                    const int i = i0 + 5 * it;
+                    const double x = sB[i * NS + p], y = sB[i * NS + q];
+                    sB[i * NS + p] = c * x - s * y; sB[i * NS + q] = s * x + c * y;
+                    const double vx = sV[i * NS + p], vy = sV[i * NS + q];
+                    sV[i * NS + p] = c * vx - s * vy; sV[i * NS + q] = s * vx + c * vy;
+                }
+            }
+            __syncthreads();
+            if (lane < 50) {
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {  // rows p, q of B
+                    const int j = i0 + 5 * it;
+                    const double x = sB[p * NS + j], y = sB[q * NS + j];
+                    sB[p * NS + j] = c * x - s * y; sB[q * NS + j] = s * x + c * y;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (lane < NS) sOrd[lane] = lane;             // (a non-finite input ranks nothing: every index stays in range)
+    __syncthreads();
+    if (lane < NS) {                              // eigenvalues descending, ties in index order (the host's stable sort)
+        const double d = sB[lane * (NS + 1)];
+        int rank = 0;
+        for (int j = 0; j < NS; ++j) { const double dj = sB[j * (NS + 1)]; rank += (dj > d || (dj == d && j < lane)) ? 1 : 0; }
+        sOrd[rank] = lane;
+    }
+    __syncthreads();
+    ModelDev *__restrict__ out = rq.out;
+    for (int e = lane; e < NS * NS; e += MODEL_THREADS) {
+        const int i = e / NS, r = e % NS;
+        const double v = sV[i * NS + sOrd[r]];
+        out->U[i * NS + r] = v / sRt[i];
+        out->Uinv[r * NS + i] = v * sRt[i];
+        out->UinvT[i * NS + r] = v * sRt[i];
+    }
+    if (lane < NS) { out->eval[lane] = sB[sOrd[lane] * (NS + 1)]; out->pi[lane] = sPi[lane]; }
+}
+
+// ------------------------------------------------------------------------------------------
 // Branch Newton (makenewz): the pieces k_newton and the fused form inside k_oplist<11> share.  Both forms MUST produce the same
 // bits (the unfused + no-exchange form is the fallback of the fused one), so everything from a sumtable row to the Newton
 // step is written once, with floating-point contraction pinned where the two call sites could otherwise be compiled differently:
@@ -1386,6 +1505,9 @@ void launch_eigfrags(const ModelDev *model, double *frags2, hipStream_t s) {
 }
 void launch_eigfrags_n(const ModelDev *models, double *frags2, int n, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_eigfrags, dim3((unsigned)n), dim3(256), 0, s, models, frags2);
+}
+void launch_model_build(const ModelReq *reqs, int n, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    if (n > 0) hipExtLaunchKernelGGL(k_model, dim3((unsigned)n), dim3(MODEL_THREADS), 0, s, start, stop, 0, reqs);
 }
 static long long newton_timeout_ticks();
 static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, int bpg, bool one_part, bool any_pitch, bool chained, hipStream_t s, NewtonCtl *ctl,

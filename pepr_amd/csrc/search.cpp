@@ -599,7 +599,11 @@ int Batch::search(bool nni, int spr_radius, bool opt_alpha_flag, double eps, dou
     }
     newton_tol = 1e-6;                    // candidate ranking and local moves: coarse Newton
     struct Restore { double &r; ~Restore() { r = 1e-8; } } restore{newton_tol};
+    // PROTGAMMAGTR: the rates are estimated on the start tree, held fixed while the topology moves, and re-estimated once
+    // with the final optimisation
     if (int rc = optimize(opt_alpha_flag, 0.1, lnl.data())) return rc;
+    rates_on = false;
+    struct RatesBack { bool &r; ~RatesBack() { r = true; } } rates_back{rates_on};
     std::vector<char> active(n, (nni || spr_radius > 0) ? 1 : 0);
     for (int outer = 0; outer < 20; ++outer) {
         bool any = false; for (char a : active) any |= a;
@@ -628,6 +632,7 @@ int Batch::search(bool nni, int spr_radius, bool opt_alpha_flag, double eps, dou
     }
     if (trace) fprintf(stderr, "[pml] before final optimize: passes %ld smooth-steps %ld nni-steps %ld spr-steps %ld evals %ld\n", cnt_passes, cnt_smooth, cnt_nni, cnt_spr, cnt_eval);
     newton_tol = 1e-8;
+    rates_on = true;
     if (int rc = optimize(opt_alpha_flag, eps, lnl.data())) return rc;
     if (trace) fprintf(stderr, "[pml] search done: passes %ld smooth-steps %ld nni-steps %ld spr-steps %ld evals %ld\n", cnt_passes, cnt_smooth, cnt_nni, cnt_spr, cnt_eval);
     if (trace) fprintf(stderr, "[pml] host ms: pass set-up %.1f, pass steps (overlapped) %.1f, pass sync wait %.1f, pass post %.1f, nni build %.1f, nni run %.1f, nni select %.1f, alpha host %.1f, builds of synchronised launches %.1f\n",

@@ -159,12 +159,32 @@ int main(int argc, char **argv) {
         else return fail(tool, "unknown option " + a);
     }
     if (aln_f.empty() || run.empty()) return fail(tool, "usage: raxmlHPC -f d|e|g -m PROTGAMMAWAG -s aln.phy -n run [-t tree] [-z trees]");
-    // two models are built: PROTGAMMAWAG and PROTGAMMAWAGF (the same exchangeabilities with frequencies counted from the
-    // alignment); PROTCATWAG, PROTGAMMAIWAG and the other matrices -matrix_eval may pass (PhylogenomicPipeline2.java:260-284:
-    // their tables are not in the reference) are different likelihood functions and are refused rather than run as WAG
-    // under their name
-    if (model_s != "PROTGAMMAWAG" && model_s != "PROTGAMMAWAGF") return fail(tool, "only -m PROTGAMMAWAG and PROTGAMMAWAGF are built, got " + model_s);
-    const int pi_mode_s = model_s == "PROTGAMMAWAGF" ? PML_PI_EMPIRICAL : PML_PI_RAXML_3DP;
+    // Built in: PROTGAMMAWAG, PROTGAMMAWAGF (the same exchangeabilities with frequencies counted from the alignment) and
+    // PROTGAMMAGTR (exchangeabilities estimated from the alignment).  Any other PROTGAMMA<NAME> / PROTGAMMA<NAME>F is the
+    // matrix of the PAML file <name>.dat (lower case) in the directory $PEPRML_MODEL_DIR; no table ships with the engine
+    // (the ones -matrix_eval may pass, PhylogenomicPipeline2.java:260-284, are not in the reference).  A name whose table
+    // is not there is refused, never run as WAG under its label; PROTCAT*, PROTGAMMAI*, PROTMIX* and the nucleotide models
+    // are different likelihood functions and stay refused.
+    int pi_mode_s = PML_PI_RAXML_3DP;
+    std::string matrix_file, matrix_name; bool matrix_f = false; double m_exch[190], m_pi[20];
+    if (model_s == "PROTGAMMAWAGF") pi_mode_s = PML_PI_EMPIRICAL;
+    else if (model_s == "PROTGAMMAGTR") pi_mode_s = PML_PI_GTR;
+    else if (model_s != "PROTGAMMAWAG") {
+        const char *dir = std::getenv("PEPRML_MODEL_DIR");
+        std::string name = model_s.rfind("PROTGAMMA", 0) == 0 ? model_s.substr(9) : "";
+        bool ok = dir && *dir && !name.empty() && name[0] != 'I';
+        for (char &c : name) { if (!std::isalnum((unsigned char)c)) ok = false; c = (char)std::tolower((unsigned char)c); }
+        if (ok) {
+            matrix_file = std::string(dir) + "/" + name + ".dat"; matrix_name = name;
+            if (!std::ifstream(matrix_file) && name.size() > 1 && name.back() == 'f') {
+                matrix_name = name.substr(0, name.size() - 1); matrix_file = std::string(dir) + "/" + matrix_name + ".dat"; matrix_f = true;
+            }
+            ok = (bool)std::ifstream(matrix_file);
+        }
+        if (!ok) return fail(tool, "only -m PROTGAMMAWAG, PROTGAMMAWAGF and PROTGAMMAGTR are built in (PROTGAMMA<NAME>[F] needs <name>.dat in $PEPRML_MODEL_DIR), got " + model_s);
+        if (int prc = pml_matrix_parse_paml(read_file(matrix_file.c_str()).c_str(), m_exch, m_pi))
+            return fail(tool, matrix_file + ": " + pml_strerror(prc) + " " + pml_last_error(nullptr));
+    }
     if (std::ifstream("RAxML_info." + run)) return fail(tool, "RAxML output files with the run ID <" + run + "> already exist");
     if (f == "b") {                                       // RAxMLRunner.java:453-516: draw the bipartition frequencies of -z trees on -t tree (host only)
         if (tree_f.empty() || trees_f.empty()) return fail(tool, "-f b needs -t tree -z trees");
@@ -190,9 +210,16 @@ int main(int argc, char **argv) {
     pml_ctx *ctx = nullptr; pml_config cfg = {0, 0, 0};
     if (int rc = pml_create(&cfg, &ctx)) return fail(tool, std::string("engine: ") + pml_strerror(rc) + " " + pml_last_error(nullptr));
     std::vector<const char *> np, rp; pml_alignment v = view(a, np, rp);
+    if (!matrix_file.empty()) {
+        int code = 0;
+        if (int mrc = pml_matrix_register(ctx, matrix_name.c_str(), m_exch, m_pi, &code)) { std::string m = pml_last_error(ctx); pml_destroy(ctx); return fail(tool, m + " (" + pml_strerror(mrc) + ")"); }
+        pi_mode_s = code + (matrix_f ? 1 : 0);
+    }
     pml_model model = {4, 1.0, pi_mode_s};
     std::ofstream info("RAxML_info." + run), logf("RAxML_log." + run);
     info << "peprml raxmlHPC shim (MI355X HIP engine), model " << model_s << ", alignment " << aln_f << "\n";
+    if (!matrix_file.empty()) info << "rate matrix read from " << matrix_file << (matrix_f ? " (empirical frequencies)" : "") << "; parity unpinned (the table is the installer's)\n";
+    if (pi_mode_s == PML_PI_GTR) info << "exchangeabilities estimated from the alignment (start: WAG, bounds 1e-7 .. 1e6); parity unpinned\n";
     int rc = 0;
     if (f == "a") {                                       // RAxMLRunner.java:115-132 with bootstrapReps > 0
         if (bs_reps <= 0) { pml_destroy(ctx); return fail(tool, "-f a needs -x seed -N reps"); }
@@ -245,7 +272,24 @@ int main(int argc, char **argv) {
         while (std::getline(tf, line)) { bool blank = true; for (char c : line) if (!std::isspace((unsigned char)c)) blank = false; if (!blank) trees.push_back(line); }
         std::ofstream out("RAxML_perSiteLLs." + run);
         out << "  " << trees.size() << "  " << v.nsites << "\n";
-        for (size_t i = 0; i < trees.size() && !rc; ++i) {
+        for (size_t i = 0; i < trees.size() && !rc && pi_mode_s == PML_PI_GTR; ++i) {
+            // the estimated matrix lives in the batch: optimise and read the per-site values from the same resident batch
+            pml_search_opts opts = {1, 0, 0, 1e-4, 0};
+            pml_batch *b = nullptr; const char *nw = trees[i].c_str(); double lnl = 0;
+            rc = pml_batch_create(ctx, 1, &v, &nw, &model, &b);
+            if (rc) break;
+            rc = pml_batch_optimize(b, &opts, &lnl, nullptr);
+            std::vector<double> sl((size_t)v.nsites + 1);
+            if (!rc) rc = pml_batch_site_lnl(b, 0, sl.data());
+            if (!rc) {
+                out << "tr" << (i + 1) << "\t";
+                char bf[64];
+                for (int s = 0; s < v.nsites; ++s) { std::snprintf(bf, sizeof bf, "%.6f ", sl[s]); out << bf; }
+                out << "\n";
+            }
+            pml_batch_destroy(b);
+        }
+        for (size_t i = 0; i < trees.size() && !rc && pi_mode_s != PML_PI_GTR; ++i) {
             pml_search_opts opts = {1, 0, 0, 1e-4, 0};
             pml_result o, r;
             rc = pml_optimize(ctx, &v, trees[i].c_str(), &model, &opts, &o);     // -f g optimises model + lengths per tree

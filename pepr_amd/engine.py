@@ -9,8 +9,10 @@ import numpy as np
 from . import _lib
 
 KERNELS = {"pmat": 0, "newview": 1, "evaluate": 2, "sumtable": 3, "newton": 4, "reduce": 5,
-           "host_build": 6, "host_wait": 7}
+           "host_build": 6, "host_wait": 7, "model": 8}
 PI_RAXML_3DP, PI_WAG_FULL, PI_EMPIRICAL = 0, 1, 2      # PI_EMPIRICAL = PROTGAMMAWAGF (frequencies counted per gene)
+PI_GTR = 3             # PROTGAMMAGTR: exchangeabilities estimated per gene by the optimising calls, empirical frequencies
+MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
 
 class PmlError(RuntimeError):
@@ -88,6 +90,20 @@ def constraints_from_tree(newick):
     taxa = sorted(node())
     rows = ["".join("1" if t in c else "0" for c in cols) for t in taxa]
     return taxa, rows
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def parse_paml(text):
+    """PAML .dat text -> (190 exchangeabilities: lower triangle by rows, 20 frequencies), state order ARNDCQEGHILKMFPSTWYV"""
+    L = _lib.load()
+    ex, pi = np.zeros(190), np.zeros(20)
+    rc = L.pml_matrix_parse_paml(text.encode() if isinstance(text, str) else text, _dp(ex), _dp(pi))
+    if rc:
+        raise PmlError(rc, L.pml_last_error(None).decode())
+    return ex, pi
 
 
 class Context:
@@ -283,6 +299,44 @@ class Context:
         self._check(self.L.pml_coalescing_stats(self.ptr, C.byref(b), C.byref(r)))
         return {"batches": b.value, "requests": r.value}
 
+    def register_matrix(self, name, exch190, pi20):
+        """-> model code: `code` = this matrix with its own frequencies, `code + 1` = with each gene's empirical frequencies"""
+        ex, pi = np.ascontiguousarray(exch190, dtype=np.float64), np.ascontiguousarray(pi20, dtype=np.float64)
+        assert ex.shape == (190,) and pi.shape == (20,)
+        code = C.c_int()
+        self._check(self.L.pml_matrix_register(self.ptr, name.encode(), _dp(ex), _dp(pi), C.byref(code)))
+        return code.value
+
+    def model_eval(self, gene, newick, codes, optimize_alpha=True, epsilon=1e-4):
+        """one tree optimised under each model code in ONE device batch -> (results as optimize_one gives them, index of the best)"""
+        keep = []
+        aln = _aln_struct(gene[0], gene[1], keep)
+        n = len(codes)
+        cs = (C.c_int * n)(*codes)
+        o = _opts(optimize_alpha, False, 0, epsilon)
+        res = (_lib.Result * n)()
+        best = C.c_int(-1)
+        rc = self.L.pml_model_eval(self.ptr, C.byref(aln), newick.encode(), n, cs, C.byref(o), res, C.byref(best))
+        out = []
+        if rc == 0:
+            out = [{"lnl": r.lnl, "alpha": r.alpha, "tree_length": r.tree_length, "npatterns": r.npatterns, "nsites": r.nsites,
+                    "newick": C.string_at(r.newick).decode() if r.newick else None} for r in res]
+        for r in res:
+            self.L.pml_result_free(C.byref(r))
+        self._check(rc)
+        return out, best.value
+
+    def debug_model_build(self, exch, pi):
+        """k_model on n matrices (n x 190, n x 20) -> list of dicts eval / U / Uinv / pi / UinvT, and the raw n x 1240 array"""
+        ex, p = np.ascontiguousarray(exch, dtype=np.float64), np.ascontiguousarray(pi, dtype=np.float64)
+        n = ex.shape[0]
+        assert ex.shape == (n, 190) and p.shape == (n, 20)
+        raw = np.zeros((n, MODELDEV_DOUBLES))
+        self._check(self.L.pml_debug_model_build(self.ptr, n, _dp(ex), _dp(p), _dp(raw)))
+        out = [{"eval": r[:20].copy(), "U": r[20:420].reshape(20, 20).copy(), "Uinv": r[420:820].reshape(20, 20).copy(),
+                "pi": r[820:840].copy(), "UinvT": r[840:1240].reshape(20, 20).copy()} for r in raw]
+        return out, raw
+
     def newton_fallbacks(self):
         """how often k_newton's bounded exchange wait gave up on this context and work was re-issued through the no-exchange form"""
         a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -346,6 +400,19 @@ class Batch:
 
     def set_alpha(self, alpha, g=-1):
         self.ctx._check(self.L.pml_batch_set_alpha(self.ptr, g, alpha))
+
+    def set_matrix(self, exch190, pi20=None, g=-1):
+        """the rate matrix of gene g (-1: all genes); pi20 None keeps the frequencies.  Any batch becomes a per-gene-model batch."""
+        ex = np.ascontiguousarray(exch190, dtype=np.float64)
+        pi = None if pi20 is None else np.ascontiguousarray(pi20, dtype=np.float64)
+        assert ex.shape == (190,) and (pi is None or pi.shape == (20,))
+        self.ctx._check(self.L.pml_batch_set_matrix(self.ptr, g, _dp(ex), None if pi is None else _dp(pi)))
+
+    def get_matrix(self, g):
+        """(exchangeabilities, frequencies) gene g is scored with: estimates after a GTR optimisation, counted frequencies of F variants"""
+        ex, pi = np.zeros(190), np.zeros(20)
+        self.ctx._check(self.L.pml_batch_get_matrix(self.ptr, g, _dp(ex), _dp(pi)))
+        return ex, pi
 
     def root_derivs(self):
         a, b, c = np.zeros(self.n), np.zeros(self.n), np.zeros(self.n)

@@ -15,6 +15,7 @@ and ignored (the GPU engine needs no -T).  Not mirrored (out of scope, SURVEY.md
 bootstrap (-Y), nucleotide (-gtr -nt).
 """
 import logging
+import os
 
 from . import engine
 
@@ -47,19 +48,31 @@ class SequenceAlignment:
         return (self.taxa, self.rows)
 
 
-def _model_from_matrix(matrix):
+def _model_from_matrix(matrix, ctx=None):
     """RAxML -m strings PEPR passes (RAxMLRunner.java:115-132; the 23 names of -matrix_eval,
-    PhylogenomicPipeline2.java:260-284).  TWO models are built -- PROTGAMMAWAG (WAG exchangeabilities, RAxML's
-    3-decimal frequencies, Gamma4) and PROTGAMMAWAGF (the same with frequencies counted from the alignment) -- and a
-    likelihood is never reported under another model's name: PROTCATWAG, PROTGAMMAIWAG and the other matrices (whose
-    tables the reference does not hold) raise."""
+    PhylogenomicPipeline2.java:260-284).  Built in: PROTGAMMAWAG (WAG exchangeabilities, RAxML's 3-decimal
+    frequencies, Gamma4), PROTGAMMAWAGF (the same with frequencies counted from the alignment) and PROTGAMMAGTR
+    (exchangeabilities estimated from the alignment).  PROTGAMMA<NAME> / PROTGAMMA<NAME>F is the matrix of the PAML file
+    <name>.dat in the directory $PEPRML_MODEL_DIR, registered on the context; no table ships with the engine.  A
+    likelihood is never reported under another model's name: a name whose table is not there, PROTCAT*, PROTGAMMAI*,
+    PROTMIX* and the nucleotide models raise."""
     m = (matrix or "PROTGAMMAWAG").upper()
     if m == "PROTGAMMAWAGF":
         return {"ncat": 4, "pi_mode": engine.PI_EMPIRICAL}
-    if m != "PROTGAMMAWAG":
-        raise ValueError("the GPU engine implements PROTGAMMAWAG and PROTGAMMAWAGF only; %r is not built (it would be a "
-                         "different likelihood function, not a variant spelling)" % matrix)
-    return {"ncat": 4, "pi_mode": engine.PI_RAXML_3DP}
+    if m == "PROTGAMMAGTR":
+        return {"ncat": 4, "pi_mode": engine.PI_GTR}
+    if m == "PROTGAMMAWAG":
+        return {"ncat": 4, "pi_mode": engine.PI_RAXML_3DP}
+    d, name = os.environ.get("PEPRML_MODEL_DIR"), m[9:].lower() if m.startswith("PROTGAMMA") else ""
+    if d and name.isalnum() and not name.startswith("i"):
+        for stem, f in ((name, 0), (name[:-1], 1)) if name.endswith("f") and len(name) > 1 else ((name, 0),):
+            path = os.path.join(d, stem + ".dat")
+            if os.path.isfile(path):
+                ex, pi = engine.parse_paml(open(path).read())
+                return {"ncat": 4, "pi_mode": (ctx or default_context()).register_matrix(stem, ex, pi) + f}
+    raise ValueError("the GPU engine has PROTGAMMAWAG, PROTGAMMAWAGF and PROTGAMMAGTR built in and takes PROTGAMMA<NAME>[F] "
+                     "from <name>.dat in $PEPRML_MODEL_DIR; %r is not built (it would be a different likelihood function, "
+                     "not a variant spelling)" % matrix)
 
 
 class RAxMLRunner:
@@ -119,13 +132,19 @@ class RAxMLRunner:
 
     def run(self):
         """-f d (ML search) or, with setPerSiteLogLikelihoods(true), -f g on the given trees."""
-        mdl = _model_from_matrix(self.matrix)          # an unbuilt model name is refused, loudly, before any device work
+        mdl = _model_from_matrix(self.matrix, self.ctx)          # an unbuilt model name is refused, loudly, before any device work
         ctx = self.ctx or default_context()
         try:
             gene = self.alignment.as_gene()
             if self.perSiteLL:
                 self.perSiteLLs = []
                 for nw in self.perSiteLLTrees:
+                    if mdl["pi_mode"] == engine.PI_GTR:             # the estimated matrix lives in the batch that estimated it
+                        b = engine.Batch(ctx, [gene], [nw], **mdl)
+                        b.optimize()
+                        self.perSiteLLs.append(b.site_lnl(0, len(gene[1][0])))
+                        b.close()
+                        continue
                     o = ctx.optimize([gene], [nw], **mdl)[0]        # RAxML -f g optimises model + lengths first
                     r = ctx.score([gene], [o["newick"]], alpha=o["alpha"], site_lnl=True, **mdl)[0]
                     self.perSiteLLs.append(r["site_lnl"])
