@@ -563,9 +563,28 @@ __device__ __forceinline__ Rows5 load_rows(const double *tab, unsigned code, int
     r.c = *reinterpret_cast<const GLOBAL_AS double *>(p + 32);
     return r;
 }
-__device__ __forceinline__ void load_cherry(Operand &o, const OpSide &sd, unsigned ca, unsigned cb, int c, int q) {
-    const Rows5 a0 = load_rows(sd.t0, ca & 0xFFu, c, q), a1 = load_rows(sd.t0, ca >> 8, c, q);
-    const Rows5 b0 = load_rows(sd.t1, cb & 0xFFu, c, q), b1 = load_rows(sd.t1, cb >> 8, c, q);
+// the same record out of a copy of the table in LDS (the wide scoring kernel stages the two tables of one cherry / pitchfork side
+// per operation, k_oplist_wide): the same doubles whatever the code, so a pattern's bits do not depend on where its rows came
+// from.  An explicit LDS pointer: ds_read, counted on lgkmcnt like the fragment reads (LDS answers in order), never a FLAT load.
+__device__ __forceinline__ Rows5 load_rows_lds(const double *tab, unsigned code, int c, int q) {
+#ifdef ABL_NO_ROWS
+    { Rows5 r1; r1.a = (dvec2){0.9, 0.9}; r1.b = (dvec2){0.9, 0.9}; r1.c = 0.9 + 1e-9 * code; return r1; }
+#endif
+    typedef const __attribute__((address_space(3))) char *lcptr;
+    lcptr p = (lcptr)tab + ((c * NCODES + code) * 4 + q) * (TIPTAB_KK * 8);
+    Rows5 r;
+    r.a = *reinterpret_cast<const __attribute__((address_space(3))) dvec2 *>(p);
+    r.b = *reinterpret_cast<const __attribute__((address_space(3))) dvec2 *>(p + 16);
+    r.c = *reinterpret_cast<const __attribute__((address_space(3))) double *>(p + 32);
+    return r;
+}
+// LDS: the tables of t0 | t1 are the two consecutive LDS regions at sTab
+template <bool LDS = false>
+__device__ __forceinline__ void load_cherry(Operand &o, const OpSide &sd, const double *sTab, unsigned ca, unsigned cb, int c, int q) {
+    const Rows5 a0 = LDS ? load_rows_lds(sTab, ca & 0xFFu, c, q) : load_rows(sd.t0, ca & 0xFFu, c, q);
+    const Rows5 a1 = LDS ? load_rows_lds(sTab, ca >> 8, c, q) : load_rows(sd.t0, ca >> 8, c, q);
+    const Rows5 b0 = LDS ? load_rows_lds(sTab + TIPTAB_DOUBLES, cb & 0xFFu, c, q) : load_rows(sd.t1, cb & 0xFFu, c, q);
+    const Rows5 b1 = LDS ? load_rows_lds(sTab + TIPTAB_DOUBLES, cb >> 8, c, q) : load_rows(sd.t1, cb >> 8, c, q);
     o.v[0] = (dvec2){a0.a.x * b0.a.x, a1.a.x * b1.a.x};
     o.v[1] = (dvec2){a0.a.y * b0.a.y, a1.a.y * b1.a.y};
     o.v[2] = (dvec2){a0.b.x * b0.b.x, a1.b.x * b1.b.x};
@@ -576,11 +595,11 @@ __device__ __forceinline__ void load_cherry(Operand &o, const OpSide &sd, unsign
 // 40 VGPRs of raw rows live through the second contraction, 123 spills; in front of the left contraction of the same category
 // and multiplied behind it, 63 spills, C3 launch 0.60 -> 0.72 ms.)
 // pitchfork operand for category c: ((F_inner . (T_a * T_b)) * T_c), all in registers
-template <bool EARLY = true>
-__device__ __forceinline__ void load_pitch(Operand &o, const OpSide &sd, const double *__restrict__ f_inner,
+template <bool EARLY = true, bool LDS = false>
+__device__ __forceinline__ void load_pitch(Operand &o, const OpSide &sd, const double *__restrict__ f_inner, const double *sTab,
                                            unsigned ca, unsigned cb, unsigned cc, int c, int q) {
     Operand w;
-    load_cherry(w, sd, ca, cb, c, q);
+    load_cherry<LDS>(w, sd, sTab, ca, cb, c, q);
     // EARLY: the third tip's rows are requested BEFORE the inner contraction (whose scheduling fences keep everything behind it
     // where the source puts it): behind it, as first written, their L2 round trip was waited for in full, once per category
     // (C3 launch 0.570 -> 0.563 ms).  Not in the fused-Newton variant: 20 more live VGPRs there are 20 more spills (29 -> 49).
@@ -601,7 +620,9 @@ __device__ __forceinline__ void load_pitch(Operand &o, const OpSide &sd, const d
 //   MODE_SUMTABLE: same contraction with the eigen-basis matrices (no rescue), counts = l + r
 //   MODE_EVALUATE: per-pattern ln( 1/4 sum_c sum_s L_c[s] (pi P_c . R_c)[s] ) - counts*256 ln 2
 // CHAIN: register chaining (kernels.h OPF_CHAIN_*); FUSE (implies CHAIN): a sumtable tile may stay in X for newton_fused.
-template <bool CHAIN, bool FUSE>
+// TIPLDS (the wide scoring kernel): sP + 3 * PFRAG holds the tables of t0 | t1 of the operation's cherry / pitchfork side (of the
+// left one if both sides are such; the other side, and a pitchfork's third tip, keep the table rows in global memory).
+template <bool CHAIN, bool FUSE, bool TIPLDS = false>
 __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restrict__ sP, const unsigned char *__restrict__ sT,
                                          int p, int lane, Operand (&X)[4], ivec2 &xsc) {
     // `op` refers to the descriptor in global memory (wave-uniform): fields are fetched by scalar loads
@@ -650,6 +671,8 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
     // fragment read through it a FLAT load, which counts on both vmcnt and lgkmcnt -- each k-step of the inner contraction then
     // waited for everything in flight: a right-hand pitchfork cost 11 k cycles more than a right-hand cherry for 100 more MFMAs)
     const bool both_pitch = lk == SK_PITCH && rk == SK_PITCH;
+    const double *sTab = sP + 3 * PFRAG;
+    const bool ldsR = TIPLDS && lk < SK_CHERRY;             // the staged tables are the right side's (stage_frags_wide)
     const double *fRg = sdr.f + (q * 4 + (lane & 3));
 #ifdef ABL_NO_CODES      // timing-only ablation: tip codes made up from the pattern index instead of loaded
 #define CODE_LD(ptr) ((((unsigned)p * 5u + 1u + (unsigned)(size_t)(ptr)) % 20u) | ((((unsigned)p * 3u + 2u) % 20u) << 8))
@@ -687,10 +710,14 @@ __device__ __forceinline__ void chunk_op(const NvOp &op, const double *__restric
 #pragma unroll CAT_UNROLL
     for (int c = 0; c < NCAT; ++c) {
         if (FUSE) { if (chL) curL = X[c]; if (chR) curR = X[c]; }
-        if (lk == SK_CHERRY) load_cherry(curL, sdl, cl, cl2, c, q);
-        else if (lk == SK_PITCH) load_pitch<!FUSE>(curL, sdl, fLi, cl, cl2, cl3, c, q);
-        if (rk == SK_CHERRY) load_cherry(curR, sdr, cr, cr2, c, q);
-        else if (rk == SK_PITCH) { if (both_pitch) load_pitch<!FUSE>(curR, sdr, fRg, cr, cr2, cr3, c, q); else load_pitch<!FUSE>(curR, sdr, fLi, cr, cr2, cr3, c, q); }
+        if (lk == SK_CHERRY) load_cherry<TIPLDS>(curL, sdl, sTab, cl, cl2, c, q);
+        else if (lk == SK_PITCH) load_pitch<!FUSE, TIPLDS>(curL, sdl, fLi, sTab, cl, cl2, cl3, c, q);
+        if (rk == SK_CHERRY) { if (ldsR) load_cherry<true>(curR, sdr, sTab, cr, cr2, c, q); else load_cherry(curR, sdr, sTab, cr, cr2, c, q); }
+        else if (rk == SK_PITCH) {
+            if (both_pitch) load_pitch<!FUSE>(curR, sdr, fRg, sTab, cr, cr2, cr3, c, q);
+            else if (ldsR) load_pitch<!FUSE, true>(curR, sdr, fLi, sTab, cr, cr2, cr3, c, q);
+            else load_pitch<!FUSE>(curR, sdr, fLi, sTab, cr, cr2, cr3, c, q);
+        }
         if (mode >= MODE_EVALUATE) {
             if (DIRECT_IN && chL) contract_stream(fR + c * 25 * 16, curR, [&](int st, double y0, double y1) { site0 += X[c].v[st].x * y0; site1 += X[c].v[st].y * y1; });
             else if (DIRECT_IN && chR) contract_stream(fR + c * 25 * 16, X[c], [&](int st, double y0, double y1) { site0 += curL.v[st].x * y0; site1 += curL.v[st].y * y1; });
@@ -826,6 +853,45 @@ __device__ __forceinline__ void stage_frags_dma3(const NvOp &op, double *dst, in
     if (inner != nullptr) dma_chunk(inner, dst + 2 * PFRAG, (wv + 2) & 3, lane);
 }
 
+// The wide scoring kernel (k_oplist_wide: eight waves, the CU's LDS to itself): the same three sets dealt over eight waves, plus
+// the tip tables t0 | t1 (17.25 KiB-rows each) of the operation's cherry / pitchfork side -- of the left one if both sides are
+// such -- into the two regions behind the sets.  9 instructions per wave (12 for wave 5 when there is an inner set).
+__device__ __forceinline__ void dma_rows4(const double *src, double *lds, int row, int lane) {
+    const GLOBAL_AS char *s = (const GLOBAL_AS char *)src + row * 1024 + lane * 16;
+    __attribute__((address_space(3))) char *d = (__attribute__((address_space(3))) char *)lds + row * 1024;
+    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)s, (__attribute__((address_space(3))) void *)d, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)s, (__attribute__((address_space(3))) void *)d, 16, 1024, 0);
+    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)s, (__attribute__((address_space(3))) void *)d, 16, 2048, 0);
+    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)s, (__attribute__((address_space(3))) void *)d, 16, 3072, 0);
+}
+__device__ __forceinline__ void dma_row(const double *src, double *lds, int row, int lane, int nlanes) {
+    const GLOBAL_AS char *s = (const GLOBAL_AS char *)src + row * 1024 + lane * 16;
+    __attribute__((address_space(3))) char *d = (__attribute__((address_space(3))) char *)lds + row * 1024;
+    if (lane < nlanes) __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)s, (__attribute__((address_space(3))) void *)d, 16, 0, 0);
+}
+static_assert(PFRAG * 8 == 12 * 1024 + 32 * 16 && TIPTAB_DOUBLES * 8 == 17 * 1024 + 16 * 16, "rows of a fragment set and of a tip table");
+__device__ __forceinline__ void stage_frags_wide(const NvOp &op, double *dst, int lane, int wave) {
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const double *pl = op.pl, *pr = op.pr;
+    const int lk = op.flags & 3, rk = (op.flags >> 2) & 3;
+    const double *inner = (lk == SK_PITCH) ? op.l.f : (rk == SK_PITCH) ? op.r.f : nullptr;
+    const double *L = pl ? pl : pr, *R = pr ? pr : pl;
+    if (wv < 3) dma_rows4(L, dst, 4 * wv, lane);
+    else if (wv < 6) dma_rows4(R, dst + PFRAG, 4 * (wv - 3), lane);
+    else dma_row(wv == 6 ? L : R, wv == 6 ? dst : dst + PFRAG, 12, lane, 32);
+    if (inner != nullptr) {
+        if (wv >= 5) dma_rows4(inner, dst + 2 * PFRAG, 4 * (wv - 5), lane);
+        else if (wv == 4) dma_row(inner, dst + 2 * PFRAG, 12, lane, 32);
+    }
+    if (lk >= SK_CHERRY || rk >= SK_CHERRY) {
+        const double *ta = lk >= SK_CHERRY ? op.l.t0 : op.r.t0, *tb = lk >= SK_CHERRY ? op.l.t1 : op.r.t1;
+        double *da = dst + 3 * PFRAG, *db = da + TIPTAB_DOUBLES;
+        if (wv < 4) dma_rows4(ta, da, 4 * wv, lane); else dma_rows4(tb, db, 4 * (wv - 4), lane);
+        if (wv < 2) dma_row(ta, da, 16 + wv, lane, wv == 0 ? 64 : 16);
+        else if (wv < 4) dma_row(tb, db, 14 + wv, lane, wv == 2 ? 64 : 16);
+    }
+}
+
 // Fused branch Newton (OPF_FUSED_NEWTON): the workgroups of one gene -- one 128-pattern tile of the sumtable each, in X --
 // iterate makenewz in place.  Same per-pattern order, finishing lanes, wave sums, exchange and step control as k_newton
 // (shared helpers above), hence its bits: waves 0 / 1 are k_newton's service waves A / B (80 exponentials per evaluation by
@@ -925,20 +991,28 @@ namespace pml {
 //       three regions per parity = 77 KB of dynamic LDS (2 workgroups per CU leave 80 KB each).  Without it: one set of regions,
 //       filled by the workgroup's own loads between two barriers.
 // FUSE (on top of both): fused branch Newton (OPF_FUSED_NEWTON) and ticketed slots.
-// Four instantiations exist (names below); launch_oplist_one chooses among them.  (Measured against them and dropped: one
+// Four 256-thread instantiations and the wide scoring kernel exist (names below); launch_oplist_one chooses among them.  (Measured against them and dropped: one
 // pattern per lane at 4 waves per SIMD with chaining kept, 0.797 against 0.676 ms per C3 scoring launch, 46 spills, DESIGN.md 9
 // r03-g; the plain kernel at 3 waves per SIMD, with CLV rows one category ahead or with LDS-DMA staging, never the default.
 // DESIGN.md 4 says where their source can be read.)
-template <bool CHAIN, bool DBUF, bool FUSE>
-__global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
+// WAVES = 8 (k_oplist_wide, CHAIN and DBUF, no FUSE): a 512-thread workgroup owns two consecutive tiles (256 patterns) and is alone
+//       on its CU, still 2 waves per SIMD at 256 VGPRs.  Eight waves share one staging of the operation's sets and one barrier, and
+//       the LDS a second workgroup would have had holds tip tables (chunk_op TIPLDS).  LDS map, per parity: left | right | inner
+//       fragment sets (3 x 12 800 B) | tables of t0 | t1 of one cherry / pitchfork side (2 x 17 664 B) = 73 728 B; two parities and
+//       the 512 B indicator table: 147 968 B.  (Three tables per parity do not fit the CU's 163 840 B.)
+template <bool CHAIN, bool DBUF, bool FUSE, int WAVES>
+__device__ __forceinline__ void oplist_body(
         const NvOp *__restrict__ ops, const GeneRun *__restrict__ runs, int nruns, int blocks_per_gene, int any_pitch,
         NewtonCtl *ctl, long long timeout_ticks) {
     static_assert(CHAIN || !DBUF, "LDS-DMA staging exists for the chained kernels only");
     static_assert(!FUSE || (CHAIN && DBUF), "the fused-Newton kernel is the scoring kernel plus the Newton code");
+    static_assert(WAVES == 4 || (WAVES == 8 && CHAIN && DBUF && !FUSE), "eight waves: the scoring kernel only");
+    constexpr bool WIDE = WAVES == 8;
+    constexpr int WG_PAT = WAVES * PAT_PER_WAVE;
 #ifdef PML_OPTIME
     const long long t_life0 = clock64();
 #endif
-    constexpr int PARITY_STRIDE = 3 * PFRAG;
+    constexpr int PARITY_STRIDE = 3 * PFRAG + (WIDE ? 2 * TIPTAB_DOUBLES : 0);
     Operand X[4]; ivec2 xsc = {0, 0};
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -947,8 +1021,8 @@ __global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
     // dynamic LDS: [left|right] fragments (x2 when double-buffered) [+ left-inner|right-inner fragments of
     // pitchfork sides when the launch has any] + the float tip-indicator table
     extern __shared__ double sP[];
-    const int nfrag_regions = DBUF ? 6 : 2 + (any_pitch ? 1 : 0);
-    unsigned char *sT = reinterpret_cast<unsigned char *>(sP + nfrag_regions * PFRAG);
+    const int nfrag_doubles = DBUF ? 2 * PARITY_STRIDE : (2 + (any_pitch ? 1 : 0)) * PFRAG;
+    unsigned char *sT = reinterpret_cast<unsigned char *>(sP + nfrag_doubles);
     // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share
     // an XCD and its L2), so all pattern blocks of one gene get the same blockIdx % 8: the gene's
     // transition-matrix fragments are then fetched into ONE L2 instead of eight (speed only).
@@ -986,15 +1060,16 @@ __global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
     const GeneRun run = runs[gi];
     if (run.op_begin >= run.op_end) { leave(); return; }
     const int mpad = ops[run.op_begin].mpad;            // constant per gene
-    if (blk * PAT_PER_WG >= mpad) { leave(); return; }
-    const int p = (blk * 4 + wave) * PAT_PER_WAVE + 2 * (lane & 15);
-    const bool active = (blk * 4 + wave) * PAT_PER_WAVE < mpad;
+    if (blk * WG_PAT >= mpad) { leave(); return; }
+    const int p = (blk * WAVES + wave) * PAT_PER_WAVE + 2 * (lane & 15);
+    const bool active = (blk * WAVES + wave) * PAT_PER_WAVE < mpad;
 
 #ifdef PML_OPTIME
     const long long t_start1 = clock64();        // slot claimed, run descriptor read
 #endif
-    for (int i = tid; i < TIPTAB; i += 256) sT[i] = (unsigned char)((code_mask(i / NS) >> (i % NS)) & 1u);
-    if (DBUF) stage_frags_dma3(ops[run.op_begin], sP, lane, wave);
+    for (int i = tid; i < TIPTAB; i += 64 * WAVES) sT[i] = (unsigned char)((code_mask(i / NS) >> (i % NS)) & 1u);
+    auto stage = [&](const NvOp &o, double *dst) { if (WIDE) stage_frags_wide(o, dst, lane, wave); else stage_frags_dma3(o, dst, lane, wave); };
+    if (DBUF) stage(ops[run.op_begin], sP);
     __syncthreads();
 #ifdef PML_OPTIME
     const long long t_start2 = clock64();        // tip table filled, first fragment sets staged and landed
@@ -1006,7 +1081,7 @@ __global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
         if (DBUF) {
             const int par = (oi - run.op_begin) & 1;
             buf = sP + par * PARITY_STRIDE;
-            if (oi + 1 < run.op_end) stage_frags_dma3(ops[oi + 1], sP + (par ^ 1) * PARITY_STRIDE, lane, wave);
+            if (oi + 1 < run.op_end) stage(ops[oi + 1], sP + (par ^ 1) * PARITY_STRIDE);
         } else {
             if (oi > run.op_begin) __syncthreads();      // previous op: LDS reads and global stores complete
             const double2 *gl = reinterpret_cast<const double2 *>(op.pl);
@@ -1030,7 +1105,7 @@ __global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
         const long long t_op0 = clock64();
 #endif
 #ifndef ABL_NO_OP        // timing-only ablation: the shell alone (descriptor reads, fragment staging, barriers)
-        if (active) chunk_op<CHAIN, FUSE>(op, buf, sT, p, lane, X, xsc);
+        if (active) chunk_op<CHAIN, FUSE, WIDE>(op, buf, sT, p, lane, X, xsc);
 #endif
 #ifdef PML_OPTIME
         if (lane == 0 && active) {
@@ -1068,11 +1143,23 @@ __global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
 #endif
     leave();
 }
+template <bool CHAIN, bool DBUF, bool FUSE>
+__global__ __launch_bounds__(256, CHAIN ? PML_CHAIN_WAVES : 4) void k_oplist(
+        const NvOp *__restrict__ ops, const GeneRun *__restrict__ runs, int nruns, int blocks_per_gene, int any_pitch,
+        NewtonCtl *ctl, long long timeout_ticks) {
+    oplist_body<CHAIN, DBUF, FUSE, 4>(ops, runs, nruns, blocks_per_gene, any_pitch, ctl, timeout_ticks);
+}
+// blocks_per_gene counts 256-pattern workgroups here
+__global__ __launch_bounds__(512, PML_CHAIN_WAVES) void k_oplist_wide(
+        const NvOp *__restrict__ ops, const GeneRun *__restrict__ runs, int nruns, int blocks_per_gene, int any_pitch,
+        NewtonCtl *ctl, long long timeout_ticks) {
+    oplist_body<true, true, false, 8>(ops, runs, nruns, blocks_per_gene, any_pitch, ctl, timeout_ticks);
+}
 
-// the four op-list kernels
+// the op-list kernels
 constexpr auto k_oplist_plain = k_oplist<false, false, false>;     // formerly k_oplist<1>: no chained operand, 128 VGPRs, 4 waves per SIMD
 constexpr auto k_oplist_chain1 = k_oplist<true, false, false>;     // formerly k_oplist<9>: chained, one set of fragment regions (25.6-38.4 KB)
-constexpr auto k_oplist_score = k_oplist<true, true, false>;       // formerly k_oplist<11>: chained, double-buffered; the scoring kernel
+constexpr auto k_oplist_score = k_oplist<true, true, false>;       // formerly k_oplist<11>: chained, double-buffered; the scoring kernel of one-tile launches (k_oplist_wide takes the others)
 // formerly k_oplist<15>: the launches of the search that carry Newton tails; a kernel of its own so that the Newton code (exp, log,
 // exchange) costs the scoring kernel no register
 constexpr auto k_oplist_newton = k_oplist<true, true, true>;
@@ -1538,6 +1625,7 @@ static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, i
     const int ap = any_pitch ? 1 : 0;
     const size_t lds_single = (size_t)(2 + ap) * PFRAG * sizeof(double) + 512;     // 38.9 KB with pitchforks: 4 per CU
     const size_t lds_double = (size_t)6 * PFRAG * sizeof(double) + 512;            // 77.3 KB: two workgroups per CU, which is what 256 VGPRs allow anyway
+    const size_t lds_wide = (size_t)2 * (3 * PFRAG + 2 * TIPTAB_DOUBLES) * sizeof(double) + 512;      // 144.5 KB
     if (!chained) {                                      // only the chained kernels honour OPF_CHAIN_* flags in the descriptors
         hipExtLaunchKernelGGL(k_oplist_plain, grid, block, lds_single, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
         return;
@@ -1549,7 +1637,18 @@ static void launch_oplist_one(const NvOp *ops, const GeneRun *runs, int nruns, i
     }();
     // PML_CHAIN_VARIANT=9 (tests/test_gpu_chaining.py): the single-buffered chained kernel, which also does the scoring kernel's
     // work when 77 KB of dynamic LDS are refused
-    static const bool want_chain1 = std::getenv("PML_CHAIN_VARIANT") && std::atoi(std::getenv("PML_CHAIN_VARIANT")) == 9;
+    static const int variant = std::getenv("PML_CHAIN_VARIANT") ? std::atoi(std::getenv("PML_CHAIN_VARIANT")) : 0;
+    static const bool want_chain1 = variant == 9;
+    // The wide kernel (512 threads, 256 patterns per workgroup, 144.5 KB of LDS: one workgroup per CU) takes the chained launches
+    // without Newton tails whose largest gene has more than one tile: a gene of one tile would leave four of its eight waves, half a
+    // CU, idle.  PML_CHAIN_VARIANT=11 (tests/test_gpu_score_wide.py): the 256-thread scoring kernel, which also does its work
+    // when the runtime refuses that much LDS.
+    static const hipError_t big_wide = hipFuncSetAttribute(reinterpret_cast<const void *>(k_oplist_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide);
+    if (!ctl && !one_part && variant == 0 && big_wide == hipSuccess && bpg_in > 1) {
+        const int bpg_wide = (bpg_in + 1) / 2;
+        hipExtLaunchKernelGGL(k_oplist_wide, dim3((unsigned)(((nruns + 7) / 8) * 8 * bpg_wide)), dim3(512), lds_wide, s, start, stop, 0, ops, runs, nruns, bpg_wide, ap, ctl, to);
+        return;
+    }
     if (ctl) hipExtLaunchKernelGGL(k_oplist_newton, grid, block, lds_double, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
     else if (want_chain1 || big != hipSuccess) hipExtLaunchKernelGGL(k_oplist_chain1, grid, block, lds_single, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
     else hipExtLaunchKernelGGL(k_oplist_score, grid, block, lds_double, s, start, stop, 0, ops, runs, nruns, bpg, ap, ctl, to);
