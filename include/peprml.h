@@ -28,6 +28,9 @@
  *   pml_refine_next<- .../pepr/tree/PhylogeneticTreeRefiner.java:298-359 + AdvancedTree.java:1061-1098
  *   pml_support_tree<- .../pepr/tree/TreeSupportDecorator.java:86-163 addSupportValues(): integer
  *                        bipartition counts of the support trees written as node labels of the main tree
+ *   pml_tree_tests <- .../pepr/tree/TreeComparison.java:812-885 runConsel(): `raxmlHPC -f g -z trees` piped through
+ *                        `makermt -b 10 --puzzle`, `consel`, `catpv -v` -> the table of AU / KH / SH / bootstrap p-values;
+ *                        pml_rell_tests is the makermt | consel | catpv half alone, on a per-site lnL table the caller has
  *
  * Conventions: caller owns inputs (nothing is retained after return);
  * the library allocates results, the caller releases them with pml_result_free(); no files, no
@@ -279,6 +282,71 @@ int pml_bootstrap(pml_ctx *ctx, const pml_alignment *aln, const pml_model *model
 /* host-only: FASTA text (">taxon\nSEQ\n" per taxon, SequenceAlignment.java:405-416) of the
  * concatenation of the selected genes (sel == NULL: all), taxa = sorted union, '?' padding */
 int pml_concatenate(int ngenes, const pml_alignment *genes, int nsel, const int *sel, char **fasta_out);
+
+/* Tree selection tests (TreeComparison.java:812-885: makermt -b 10 --puzzle | consel | catpv -v): which of T candidate trees
+ * do the data reject?  Multiscale RELL bootstrap on the device: K scales r_k, at scale k every one of B replicates draws
+ * n_k = max(1, floor(r_k N + 0.5)) sites with replacement and sums their per-site lnL for every tree.
+ *   draws    site_j = ((mix64(base + ((k B + b) << 32) + j) >> 32) * N) >> 32 for draw j of replicate b at scale k, with
+ *            base = (seed + 1) * 0x9E3779B97F4A7C15 mod 2^64 and mix64 the finaliser of splitmix64; a site is drawn with
+ *            probability within 2^-32 of 1 / N (a relative non-uniformity of at most N / 2^32).  N < 2^31, K B < 2^32, 2 <= T <= 64.
+ *   sums     Y[k][b][t] = sum_j lnl[t][site_j], plain double additions in ascending j: a function of (seed, k, b, N, table)
+ *            alone, the same bits whatever else the call holds and whichever device path (LDS or global memory) serves it
+ *   counts   bp[k][t]: replicates of scale k whose best tree is t (the lowest index of equals), every scale.  At the scale
+ *            k1 whose n_k / N is closest to 1 (the first of equals), with L_t = sum_s lnl[t][s] in site order and
+ *            C_t = Y_t (N / n_k) - L_t:   sh[t]: max_u C_u - C_t >= max_u L_u - L_t;   kh[t]: C_u* - C_t >= L_u* - L_t with
+ *            u* = argmax_{u != t} L_u (the lowest index of equals).  The replicates are centred on their exact expectation
+ *            L_t, where CONSEL centres on the replicate mean (a second pass); the two differ by O(B^-1/2) of a replicate's spread.
+ *   p-values kh, sh, bp = np = counts / B at scale k1 (Kishino-Hasegawa 1989, Shimodaira-Hasegawa 1999); au = the approximately
+ *            unbiased test of Shimodaira 2002 fitted to the K bootstrap counts of the tree (pml_au_fit); pp = exp(L_t - max) / sum.
+ *            The weighted tests (wKH, wSH), consel's maximum-likelihood fit and its model selection are not built.  No CONSEL
+ *            binary or source is part of the reference, so parity with CONSEL's own output is NOT pinned: the definitions are
+ *            the published ones, and the tests check them against an independent restatement.
+ * Every array of pml_tree_test_result is allocated by the library; release with pml_tree_test_result_free. */
+typedef struct {
+    int nscales;                 /* 0 = 10 */
+    const double *scales;        /* nscales values r_k > 0; NULL = 0.5, 0.6 ... 1.4 (nscales 0 or 10) */
+    long long reps_per_scale;    /* B; 0 = 10 000; PEPR's `makermt -b 10` = 100 000 */
+    unsigned long long seed;
+} pml_tree_test_opts;
+typedef struct {
+    int ntrees, nscales, k1;     /* k1: the scale of np / bp / kh / sh */
+    long long nsites, reps;
+    double *scales;              /* [nscales] n_k / N as drawn */
+    long long *ndraws;           /* [nscales] n_k */
+    double *lnl;                 /* [ntrees] pml_rell_tests: L_t; pml_tree_tests: the engine's lnL of the tree (the bits of pml_optimize) */
+    double *obs;                 /* max_{u != t} L_u - L_t */
+    double *au, *np, *bp, *kh, *sh, *pp;
+    double *au_d, *au_c, *au_rss; int *au_nused;     /* the AU fit: signed distance, curvature, weighted residual sum, scales used */
+    int *rank;                   /* 1 = highest L_t; equals in index order */
+    long long *bp_count;         /* [nscales][ntrees] */
+    long long *kh_count, *sh_count;   /* [ntrees] */
+} pml_tree_test_result;
+/* host-only (no device needed): Shimodaira's weighted least squares.  Over the scales with 0 < count_k < B:
+ * z_k = -Phi^-1(count_k / B) (Phi^-1 by algorithm AS 241, PPND16), weights B phi(z_k)^2 / (p_k (1 - p_k)), fit
+ * z_k ~ d sqrt(r_k) + c / sqrt(r_k); *au = 1 - Phi(d - c), *rss = the weighted residual sum of squares.  Fewer than two usable
+ * scales, or usable scales that do not determine d and c (normal matrix singular to 1e-12 of its diagonal product: all of one
+ * r_k): *au = count[k1] / B, d = c = rss = 0 and *nused = 0 or 1 -- *nused >= 2 always means that the curve was fitted.
+ * d, c, rss, nused may be NULL. */
+int pml_au_fit(int nscales, const double *r /* n_k / N */, const long long *count, long long B, double *au, double *d, double *c,
+               double *rss, int *nused);
+/* site_lnl: ntrees rows of nsites per-site lnL, the layout of RAxML_perSiteLLs */
+int pml_rell_tests(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, const pml_tree_test_opts *opts,
+                   pml_tree_test_result *out);
+/* The whole chain: the ntrees trees are ONE device batch; search_opts != NULL optimises every tree's branch lengths (and alpha if
+ * optimize_alpha) to search_opts->epsilon (0 = 1e-4) as `raxmlHPC -f g` does before it writes per-site lnL -- nni, spr_radius,
+ * seed and constraints are not used -- and NULL scores the trees as given.  The table is built on the device from the
+ * per-pattern lnL of that batch.  site_lnl_out (optional, ntrees x nsites) receives the very values that were resampled. */
+int pml_tree_tests(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const char *const *newicks, const pml_model *model,
+                   const pml_search_opts *search_opts, const pml_tree_test_opts *test_opts, pml_tree_test_result *out,
+                   double *site_lnl_out);
+void pml_tree_test_result_free(pml_tree_test_result *r);
+/* test door of the resampling kernel (k_rell): scale k draws ndraws[k] sites; y_out (optional, small shapes) = every replicate
+ * sum Y[nscales][reps][ntrees]; the raw counts bp_out[nscales][ntrees], kh_out / sh_out[ntrees].  path: 0 = LDS when the table
+ * fits, 1 = LDS (PML_EINVAL when it does not fit), 2 = global memory; *path_used = 1 or 2.  kernel_ms_out (optional): HIP-event
+ * time of the resampling launch. */
+int pml_debug_rell(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws,
+                   long long reps, unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out,
+                   long long *sh_out, int *path_used, double *kernel_ms_out);
 
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */

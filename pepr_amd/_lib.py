@@ -20,6 +20,7 @@ SYMBOLS = [
     "pml_batch_search", "pml_batch_newick", "pml_batch_root_derivs", "pml_free",
     "pml_rf_distance", "pml_support_tree", "pml_jackknife", "pml_jackknife_draw", "pml_debug_gather", "pml_concatenate", "pml_parsimony", "pml_parsimony_batch", "pml_refine_next", "pml_bootstrap", "pml_coalescing_stats",
     "pml_matrix_parse_paml", "pml_matrix_register", "pml_model_eval", "pml_batch_set_matrix", "pml_batch_get_matrix", "pml_debug_model_build", "pml_newton_fallbacks", "pml_sh_support", "pml_sh_support_batch", "pml_gamma20", "pml_gamma20_batch", "pml_debug_fpenv", "pml_kernel_stats", "pml_kernel_flops", "pml_kernel_stats_reset",
+    "pml_au_fit", "pml_rell_tests", "pml_tree_tests", "pml_tree_test_result_free", "pml_debug_rell",
 ]
 
 
@@ -57,6 +58,19 @@ class Result(C.Structure):
     _fields_ = [("status", C.c_int), ("lnl", C.c_double), ("alpha", C.c_double),
                 ("tree_length", C.c_double), ("npatterns", C.c_int), ("nsites", C.c_int),
                 ("newick", C.c_void_p), ("site_lnl", C.POINTER(C.c_double))]
+
+
+class TreeTestOpts(C.Structure):
+    _fields_ = [("nscales", C.c_int), ("scales", C.POINTER(C.c_double)), ("reps_per_scale", C.c_longlong), ("seed", C.c_ulonglong)]
+
+
+class TreeTestResult(C.Structure):
+    _dp, _lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    _fields_ = [("ntrees", C.c_int), ("nscales", C.c_int), ("k1", C.c_int), ("nsites", C.c_longlong), ("reps", C.c_longlong),
+                ("scales", _dp), ("ndraws", _lp), ("lnl", _dp), ("obs", _dp),
+                ("au", _dp), ("np", _dp), ("bp", _dp), ("kh", _dp), ("sh", _dp), ("pp", _dp),
+                ("au_d", _dp), ("au_c", _dp), ("au_rss", _dp), ("au_nused", C.POINTER(C.c_int)), ("rank", C.POINTER(C.c_int)),
+                ("bp_count", _lp), ("kh_count", _lp), ("sh_count", _lp)]
 
 
 _lib = None
@@ -131,5 +145,12 @@ def load():
     L.pml_batch_set_matrix.argtypes = [vp, C.c_int, dp, dp]
     L.pml_batch_get_matrix.argtypes = [vp, C.c_int, dp, dp]
     L.pml_debug_model_build.argtypes = [vp, C.c_int, dp, dp, dp]
+    lp, tp, trp = C.POINTER(C.c_longlong), C.POINTER(TreeTestOpts), C.POINTER(TreeTestResult)
+    L.pml_au_fit.argtypes = [C.c_int, dp, lp, C.c_longlong, dp, dp, dp, dp, ip]
+    L.pml_rell_tests.argtypes = [vp, C.c_longlong, C.c_int, dp, tp, trp]
+    L.pml_tree_tests.argtypes = [vp, ap, C.c_int, cpp, mp, sp, tp, trp, dp]
+    L.pml_tree_test_result_free.argtypes = [trp]
+    L.pml_tree_test_result_free.restype = None
+    L.pml_debug_rell.argtypes = [vp, C.c_longlong, C.c_int, dp, C.c_int, lp, C.c_longlong, C.c_ulonglong, C.c_int, dp, lp, lp, lp, ip, dp]
     _lib = L
     return L

@@ -188,6 +188,52 @@ void launch_gather(const GatherSeg *segs, int nsegs, int max_npat, hipStream_t s
 // split when the centred advantage of its best arrangement is smaller than the observed advantage of l0
 struct ShReq { const double *l0, *l1, *l2; const int *site2pat; double *out; unsigned long long seed; int nsites, nboot; };
 void launch_sh(const ShReq *reqs, int n, hipStream_t s);
+#ifdef __HIPCC__
+// the counter hash of every device-side resampler (k_sh, k_rell): splitmix64's finaliser
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
+    return z;
+}
+#endif
+
+// Tree selection tests (CONSEL's makermt | consel | catpv, TreeComparison.java:812-885): multiscale RELL resampling of a
+// per-site lnL table and the bootstrap / KH / SH counts of every tree, one launch (rell.hip).
+//   table   X[N][tpad], site-major f64 in HBM (tpad = T rounded up to even: 16-byte rows), built by launch_rell_pack
+//   draws   replicate b of scale k draws n_k sites: site_j = ((mix64(base + ((k B + b) << 32) + j) >> 32) * N) >> 32 with
+//           base = (seed + 1) * 0x9E3779B97F4A7C15 (mod 2^64) -- no 64-bit division; a site's probability is off 1/N by at
+//           most 2^-32 (absolute), i.e. by a factor within 1 +- N / 2^32
+//   sums    Y[k][b][t] = sum_j X[site_j][t], plain f64 adds in ascending j in ONE thread's registers: a function of
+//           (seed, k, b, N, X) alone, whatever the grid, the path or the rest of the launch
+//   counts  (integer atomics: order-independent)  bp[k][t] += [t = argmax_t Y[k][b][t], lowest index of equals], every scale;
+//           at scale k1 only, with L_t = sum_s X[s][t] in site order (launch_rell_pack) and C_t = Y_t * (N / n_k) - L_t:
+//           sh[t] += [max_u C_u - C_t >= max_u L_u - L_t],   kh[t] += [C_u* - C_t >= L_u* - L_t], u* = argmax_{u != t} L_u
+//           (lowest index of equals).  The replicates are centred on their EXACT expectation L_t, not on the replicate
+//           mean CONSEL uses: one pass instead of two, and the two differ by O(B^-1/2) of a replicate's spread.
+//   paths   lds = 1: every workgroup stages the table in dynamic LDS (rows padded to an odd number of 16-byte slots, so the
+//           random b128 gathers spread over all 16 slots of a bank row) and gathers from there; lds = 0: gathers from
+//           global memory (L2 / Infinity Cache).  Same bits.
+struct RellReq {
+    const double *X;                // [N][tpad]
+    const double *L;                // [T] column sums in site order
+    const int *ndraws;              // [K] n_k
+    const double *scale;            // [K] N / n_k
+    unsigned long long *bp;         // [K][T], zeroed by the caller
+    unsigned long long *kh, *sh;    // [T]
+    double *Y;                      // optional [K][B][T] (test door)
+    unsigned long long base;        // (seed + 1) * 0x9E3779B97F4A7C15
+    unsigned B;                     // replicates per scale
+    int N, T, tpad, K, k1;
+};
+// rows of the LDS copy: tpad / 2 slots of 16 bytes rounded up to odd
+constexpr int rell_lds_slots(int tpad) { return (tpad / 2) | 1; }
+constexpr size_t rell_lds_bytes(int N, int tpad) { return (size_t)N * rell_lds_slots(tpad) * 16; }
+// X[s][t] = src[t][site2pat ? site2pat[s] : s] (t < T; the padding column is 0), then L[t] = sum_s X[s][t] in site order
+void launch_rell_pack(const double *const *src /* device array of T device pointers */, const int *site2pat, double *X, double *L,
+                      int N, int T, int tpad, hipStream_t s);
+// lds: stage in LDS (the caller has checked rell_lds_fits); returns the HIP error of the launch set-up
+hipError_t launch_rell(const RellReq &r, bool lds, hipStream_t s);
+// whether the LDS path can hold the table: the device's LDS per workgroup less the room kept for static LDS
+bool rell_lds_fits(int N, int tpad, int device);
 
 // start / stop (launch_pmat, launch_oplist without ctl, launch_reduce; both or neither): timing events that the kernel's own
 // dispatch records its start and end in.  Unlike hipEventRecord before and after the launch this puts no marker packets into

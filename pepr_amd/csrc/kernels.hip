@@ -1492,10 +1492,6 @@ __global__ __launch_bounds__(256) void k_gather(const GatherSeg *__restrict__ se
 // k_sh: SH-like local support of one split per workgroup (see ShReq).  Thread = resamples tid, tid+256, ...;
 // the three per-pattern vectors are a few KB and stay in L1/L2.  Integer hash + gathers: latency/ALU-bound, tiny.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
-    return z;
-}
 __global__ __launch_bounds__(256) void k_sh(const ShReq *__restrict__ reqs) {
     __shared__ double red[3][4];
     const ShReq r = reqs[blockIdx.x];

@@ -337,6 +337,83 @@ class Context:
                 "pi": r[820:840].copy(), "UinvT": r[840:1240].reshape(20, 20).copy()} for r in raw]
         return out, raw
 
+    # ---- tree selection tests (TreeComparison.runConsel: makermt | consel | catpv) ----
+    @staticmethod
+    def _test_opts(scales, reps, seed, keep):
+        o = _lib.TreeTestOpts(0, None, int(reps), int(seed))
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, dtype=np.float64)
+            keep.append(sc)
+            o.nscales, o.scales = len(sc), _dp(sc)
+        return o
+
+    def _test_result(self, res):
+        T, K = res.ntrees, res.nscales
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True)
+        out = {"ntrees": T, "nscales": K, "k1": res.k1, "nsites": res.nsites, "reps": res.reps,
+               "scales": arr(res.scales, K, np.float64), "ndraws": arr(res.ndraws, K, np.int64),
+               "au_nused": arr(res.au_nused, T, np.int64), "rank": arr(res.rank, T, np.int64),
+               "bp_count": arr(res.bp_count, K * T, np.int64).reshape(K, T),
+               "kh_count": arr(res.kh_count, T, np.int64), "sh_count": arr(res.sh_count, T, np.int64)}
+        for f in ("lnl", "obs", "au", "np", "bp", "kh", "sh", "pp", "au_d", "au_c", "au_rss"):
+            out[f] = arr(getattr(res, f), T, np.float64)
+        return out
+
+    def rell_tests(self, site_lnl, scales=None, reps=10000, seed=0):
+        """AU / KH / SH / BP of T trees from their per-site lnL (T x N, the rows of RAxML_perSiteLLs): multiscale RELL on the
+        device.  scales None = 0.5 ... 1.4; reps per scale (PEPR's `makermt -b 10`: 100000).  -> dict of per-tree arrays
+        (lnl, obs, au, np, bp, kh, sh, pp, au_d, au_c, au_rss, au_nused, rank) and the raw counts bp_count[K, T], kh_count, sh_count."""
+        x = np.ascontiguousarray(site_lnl, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("site_lnl must be trees x sites")
+        keep = []
+        o = self._test_opts(scales, reps, seed, keep)
+        res = _lib.TreeTestResult()
+        rc = self.L.pml_rell_tests(self.ptr, x.shape[1], x.shape[0], _dp(x), C.byref(o), C.byref(res))
+        self._check(rc)
+        out = self._test_result(res)
+        self.L.pml_tree_test_result_free(C.byref(res))
+        return out
+
+    def tree_tests(self, gene, newicks, alpha=1.0, ncat=4, pi_mode=PI_RAXML_3DP, optimize=True, optimize_alpha=True, epsilon=1e-4,
+                   scales=None, reps=10000, seed=0):
+        """The whole runConsel chain for one alignment and T candidate trees in one call: every tree optimised (optimize=False:
+        scored as given) in one device batch, the per-site lnL table built and resampled on the device.  -> the dict of
+        rell_tests plus "site_lnl" (T x N, the very values that were resampled)."""
+        keep = []
+        a = _aln_struct(gene[0], gene[1], keep)
+        T = len(newicks)
+        nw = (C.c_char_p * T)(*[s.encode() for s in newicks])
+        m = _model(ncat, alpha, pi_mode)
+        so = _opts(optimize_alpha, False, 0, epsilon)
+        o = self._test_opts(scales, reps, seed, keep)
+        res = _lib.TreeTestResult()
+        site = np.zeros((T, max(a.nsites, 1)))
+        rc = self.L.pml_tree_tests(self.ptr, C.byref(a), T, nw, C.byref(m), C.byref(so) if optimize else None, C.byref(o), C.byref(res), _dp(site))
+        self._check(rc)
+        out = self._test_result(res)
+        self.L.pml_tree_test_result_free(C.byref(res))
+        out["site_lnl"] = site[:, :a.nsites]
+        return out
+
+    def debug_rell(self, site_lnl, ndraws, reps, seed=0, path=0, want_y=True):
+        """Test door of k_rell: scale k draws ndraws[k] sites.  path 0 = auto, 1 = LDS, 2 = global memory.
+        -> {"Y": [K, reps, T] replicate sums (None unless want_y), "bp": [K, T], "kh": [T], "sh": [T], "path": 1 | 2, "ms": kernel time}"""
+        x = np.ascontiguousarray(site_lnl, dtype=np.float64)
+        T, N = x.shape
+        nd = np.ascontiguousarray(ndraws, dtype=np.int64)
+        K = len(nd)
+        lp = C.POINTER(C.c_longlong)
+        y = np.zeros((K, reps, T)) if want_y else None
+        bp, kh, sh = np.zeros((K, T), dtype=np.int64), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
+        used, ms = C.c_int(0), C.c_double(0)
+        rc = self.L.pml_debug_rell(self.ptr, N, T, _dp(x), K, nd.ctypes.data_as(lp), int(reps), int(seed), int(path), _dp(y) if want_y else None,
+                                   bp.ctypes.data_as(lp), kh.ctypes.data_as(lp), sh.ctypes.data_as(lp), C.byref(used), C.byref(ms))
+        self._check(rc)
+        return {"Y": y, "bp": bp, "kh": kh, "sh": sh, "path": used.value, "ms": ms.value}
+
     def newton_fallbacks(self):
         """how often k_newton's bounded exchange wait gave up on this context and work was re-issued through the no-exchange form"""
         a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -440,6 +517,22 @@ class Batch:
         s = C.string_at(p).decode()
         self.L.pml_free(p)
         return s
+
+
+def au_fit(r, count, B):
+    """Shimodaira's AU p-value from the bootstrap counts of one tree at the scales r (= n_k / N); host only.
+    -> {"au", "d", "c", "rss", "nused"}"""
+    L = _lib.load()
+    rr = np.ascontiguousarray(r, dtype=np.float64)
+    cc = np.ascontiguousarray(count, dtype=np.int64)
+    if rr.shape != cc.shape or rr.ndim != 1:
+        raise ValueError("r and count must be vectors of one length")
+    au, d, c, rss, nused = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
+    rc = L.pml_au_fit(len(rr), _dp(rr), cc.ctypes.data_as(C.POINTER(C.c_longlong)), int(B), C.byref(au), C.byref(d), C.byref(c),
+                      C.byref(rss), C.byref(nused))
+    if rc:
+        raise PmlError(rc)
+    return {"au": au.value, "d": d.value, "c": c.value, "rss": rss.value, "nused": nused.value}
 
 
 def rf_distance(newick_a, newick_b):

@@ -7,6 +7,7 @@ read like the reference's own call sites; every `run()` goes through the C ABI
   PhylogeneticTreeBuilder  <- .../pepr/tree/pipeline/PhylogeneticTreeBuilder.java:97-129,168-196,215-338
   RAxMLRunner              <- .../pepr/tree/RAxMLRunner.java:64-152,162-213,320-336
   FastTreeRunner           <- .../pepr/tree/FastTreeRunner.java:38-135,142-199,235
+  TreeComparison.runConsel <- .../pepr/tree/TreeComparison.java:812-885
 
 Behaviour kept from the reference: a failed build leaves the result `None` (FastTreeRunner.java:
 125-131 logs and continues; callers see a null tree string); the ML matrix is a RAxML model
@@ -258,6 +259,34 @@ class FastTreeRunner:
 
     def getResult(self):
         return self.result
+
+
+class TreeComparison:
+    """.../pepr/tree/TreeComparison.java:812-885 runConsel: `raxmlHPC -f g` on the trees, then `makermt -b 10 --puzzle`, `consel`
+    and `catpv -v` on its per-site lnL -- here one engine call (pml_tree_tests).  Not built: the weighted tests wKH / wSH
+    (catpv -v prints them after sh; the columns are left out, not filled with something else)."""
+
+    REPS = 100000          # makermt's 10 000 replicates per scale times the -b 10 of the reference's command line
+
+    def __init__(self, ctx=None, reps=None, seed=0):
+        self.ctx, self.reps, self.seed = ctx, reps or self.REPS, seed
+        self.result = None
+
+    def runConsel(self, alignment, trees, processors=None, matrix="PROTGAMMAWAG"):
+        """alignment: SequenceAlignment; trees: Newick strings; processors is accepted and ignored; matrix is resolved as
+        RAxMLRunner resolves it (an unbuilt model name raises before anything touches a device).
+        -> the lines of a `catpv -v`-shaped table, one row per tree sorted by rank (item = 1-based index into trees):
+           # rank item obs au np | bp pp kh sh |"""
+        mdl = _model_from_matrix(matrix, self.ctx)
+        ctx = self.ctx or default_context()
+        r = ctx.tree_tests(alignment.as_gene(), [str(t) for t in trees], reps=self.reps, seed=self.seed, **mdl)
+        self.result = r
+        lines = ["# reading per-site lnL of %d trees x %d sites, %d scales x %d replicates" % (r["ntrees"], r["nsites"], r["nscales"], r["reps"]),
+                 "# %4s %4s %8s %6s %6s | %6s %6s %6s %6s |" % ("rank", "item", "obs", "au", "np", "bp", "pp", "kh", "sh")]
+        for t in sorted(range(r["ntrees"]), key=lambda i: r["rank"][i]):
+            lines.append("# %4d %4d %8.1f %6.3f %6.3f | %6.3f %6.3f %6.3f %6.3f |" % (
+                r["rank"][t], t + 1, r["obs"][t], r["au"][t], r["np"][t], r["bp"][t], r["pp"][t], r["kh"][t], r["sh"][t]))
+        return lines
 
 
 class PhylogeneticTreeBuilder:
