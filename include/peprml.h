@@ -298,9 +298,23 @@ int pml_concatenate(int ngenes, const pml_alignment *genes, int nsel, const int 
  *            L_t, where CONSEL centres on the replicate mean (a second pass); the two differ by O(B^-1/2) of a replicate's spread.
  *   p-values kh, sh, bp = np = counts / B at scale k1 (Kishino-Hasegawa 1989, Shimodaira-Hasegawa 1999); au = the approximately
  *            unbiased test of Shimodaira 2002 fitted to the K bootstrap counts of the tree (pml_au_fit); pp = exp(L_t - max) / sum.
- *            The weighted tests (wKH, wSH), consel's maximum-likelihood fit and its model selection are not built.  No CONSEL
+ *            consel's maximum-likelihood fit and its model selection are not built.  No CONSEL
  *            binary or source is part of the reference, so parity with CONSEL's own output is NOT pinned: the definitions are
  *            the published ones, and the tests check them against an independent restatement.
+ *   weighted (the *_weighted calls; catpv's last two columns)  For a pair of trees d_s = lnl[u][s] - lnl[t][s], mean = (sum_s d_s) / N,
+ *            sigma_ut^2 = N / (N - 1) sum_s (d_s - mean)^2: the variance of the difference of the totals (Kishino-Hasegawa 1989),
+ *            summed over the centred differences in two passes on the device (never from a Gram matrix sum x_u x_t, which
+ *            cancels about five digits at per-site lnL near -40).  sigma_ut = 0 (N = 1, or two identical columns) excludes
+ *            the pair from every weighted statistic of both trees; a tree with no pair left gets wkh = wsh = 1 and counts
+ *            equal to B.  At scale k1, over the very replicates of kh / sh:
+ *              wsh[t]: S*_t >= S_t with S_t = max_u (L_u - L_t) / sigma_ut and S*_t = max_u (C_u - C_t) / sigma_ut
+ *                      (Shimodaira-Hasegawa 1999, weighted form), u != t with sigma_ut > 0;
+ *              wkh[t]: (C_u* - C_t) / sigma_u*t >= (L_u* - L_t) / sigma_u*t with u* = argmax_u (L_u - L_t) / sigma_ut, the lowest
+ *                      index of equals.  For a fixed u* the sigma cancels: wkh differs from kh only through the choice of u*
+ *                      (the most significant competitor instead of the one with the highest lnL).
+ *            Every division is a multiplication by the precomputed 1 / sigma_ut: one rounded multiply of a rounded difference.
+ *            CONSEL estimates the variance from its replicates; here it is the exact site variance, for the reason the
+ *            replicates are centred on L_t and not on their mean: one pass less, and the two differ by O(B^-1/2).
  * Every array of pml_tree_test_result is allocated by the library; release with pml_tree_test_result_free. */
 typedef struct {
     int nscales;                 /* 0 = 10 */
@@ -347,6 +361,39 @@ void pml_tree_test_result_free(pml_tree_test_result *r);
 int pml_debug_rell(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws,
                    long long reps, unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out,
                    long long *sh_out, int *path_used, double *kernel_ms_out);
+
+/* The weighted columns of the same replicates (definitions above).  Arrays are allocated by the library; release with
+ * pml_tree_test_weighted_free. */
+typedef struct {
+    int ntrees;
+    double *wkh, *wsh;                  /* [ntrees] counts / B */
+    long long *wkh_count, *wsh_count;   /* [ntrees] */
+    double *sigma;                      /* [ntrees][ntrees] sigma_ut, 0 on the diagonal and for excluded pairs */
+    int *wkh_other;                     /* [ntrees] u*, -1 if the tree has no pair */
+} pml_tree_test_weighted;
+/* pml_rell_tests / pml_tree_tests with the weighted columns: `out` receives exactly what the unweighted call returns for the
+ * same arguments, bit for bit; `wout` the weighted columns counted over the same replicates in the same launch. */
+int pml_rell_tests_weighted(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, const pml_tree_test_opts *opts,
+                            pml_tree_test_result *out, pml_tree_test_weighted *wout);
+int pml_tree_tests_weighted(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const char *const *newicks, const pml_model *model,
+                            const pml_search_opts *search_opts, const pml_tree_test_opts *test_opts, pml_tree_test_result *out,
+                            pml_tree_test_weighted *wout, double *site_lnl_out);
+void pml_tree_test_weighted_free(pml_tree_test_weighted *w);
+/* test door of the weighted arm of k_rell and of k_rell_pairsd: pml_debug_rell's arguments and results (the same bits), plus
+ * inv_sigma_in ([ntrees][ntrees] 1 / sigma_ut: symmetric, >= 0, 0 on the diagonal, 0 = pair excluded; NULL = computed by
+ * k_rell_pairsd), inv_sigma_out (optional, the matrix that was used) and the raw counts wkh_out / wsh_out[ntrees].  The LDS path
+ * needs room for the table plus the matrix. */
+int pml_debug_rell_weighted(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws,
+                            long long reps, unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out,
+                            long long *sh_out, int *path_used, double *kernel_ms_out, const double *inv_sigma_in,
+                            double *inv_sigma_out, long long *wkh_out, long long *wsh_out);
+/* host-only: the table as runConsel's caller receives it from `catpv -v`, lines joined by '\n' (release with pml_free): a header
+ * line and one line per tree in rank order (equal ranks in index order):
+ *   "# rank item      obs     au     np |     bp     pp     kh     sh    wkh    wsh |"
+ *   "# %4d %4d %8.1f %6.3f %6.3f | %6.3f %6.3f %6.3f %6.3f %6.3f %6.3f |"      item = 1-based index of the tree
+ * w == NULL prints "-" right-aligned in the two weighted columns.  No catpv binary or source is part of the reference: the
+ * columns and their order are catpv's documented ones, the exact spacing is this project's definition. */
+int pml_catpv_table(const pml_tree_test_result *r, const pml_tree_test_weighted *w, char **out);
 
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */

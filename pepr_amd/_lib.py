@@ -21,6 +21,7 @@ SYMBOLS = [
     "pml_rf_distance", "pml_support_tree", "pml_jackknife", "pml_jackknife_draw", "pml_debug_gather", "pml_concatenate", "pml_parsimony", "pml_parsimony_batch", "pml_refine_next", "pml_bootstrap", "pml_coalescing_stats",
     "pml_matrix_parse_paml", "pml_matrix_register", "pml_model_eval", "pml_batch_set_matrix", "pml_batch_get_matrix", "pml_debug_model_build", "pml_newton_fallbacks", "pml_sh_support", "pml_sh_support_batch", "pml_gamma20", "pml_gamma20_batch", "pml_debug_fpenv", "pml_kernel_stats", "pml_kernel_flops", "pml_kernel_stats_reset",
     "pml_au_fit", "pml_rell_tests", "pml_tree_tests", "pml_tree_test_result_free", "pml_debug_rell",
+    "pml_rell_tests_weighted", "pml_tree_tests_weighted", "pml_tree_test_weighted_free", "pml_debug_rell_weighted", "pml_catpv_table",
 ]
 
 
@@ -71,6 +72,12 @@ class TreeTestResult(C.Structure):
                 ("au", _dp), ("np", _dp), ("bp", _dp), ("kh", _dp), ("sh", _dp), ("pp", _dp),
                 ("au_d", _dp), ("au_c", _dp), ("au_rss", _dp), ("au_nused", C.POINTER(C.c_int)), ("rank", C.POINTER(C.c_int)),
                 ("bp_count", _lp), ("kh_count", _lp), ("sh_count", _lp)]
+
+
+class TreeTestWeighted(C.Structure):
+    _dp, _lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    _fields_ = [("ntrees", C.c_int), ("wkh", _dp), ("wsh", _dp), ("wkh_count", _lp), ("wsh_count", _lp), ("sigma", _dp),
+                ("wkh_other", C.POINTER(C.c_int))]
 
 
 _lib = None
@@ -152,5 +159,13 @@ def load():
     L.pml_tree_test_result_free.argtypes = [trp]
     L.pml_tree_test_result_free.restype = None
     L.pml_debug_rell.argtypes = [vp, C.c_longlong, C.c_int, dp, C.c_int, lp, C.c_longlong, C.c_ulonglong, C.c_int, dp, lp, lp, lp, ip, dp]
+    twp = C.POINTER(TreeTestWeighted)
+    L.pml_rell_tests_weighted.argtypes = [vp, C.c_longlong, C.c_int, dp, tp, trp, twp]
+    L.pml_tree_tests_weighted.argtypes = [vp, ap, C.c_int, cpp, mp, sp, tp, trp, twp, dp]
+    L.pml_tree_test_weighted_free.argtypes = [twp]
+    L.pml_tree_test_weighted_free.restype = None
+    L.pml_debug_rell_weighted.argtypes = [vp, C.c_longlong, C.c_int, dp, C.c_int, lp, C.c_longlong, C.c_ulonglong, C.c_int, dp, lp, lp, lp, ip, dp,
+                                          dp, dp, lp, lp]
+    L.pml_catpv_table.argtypes = [trp, twp, C.POINTER(vp)]
     _lib = L
     return L

@@ -224,6 +224,17 @@ struct RellReq {
     unsigned B;                     // replicates per scale
     int N, T, tpad, K, k1;
 };
+// The weighted tests (wKH, wSH) of the same replicates: the weighted arm of k_rell (launch_rell_weighted) counts bp / kh / sh
+// exactly as the plain arm does and, at scale k1, from the same register sums
+//   wsh[t] += [max_u (C_u - C_t) is_ut >= S_t],  S_t = max_u (L_u - L_t) is_ut,  u != t with is_ut > 0
+//   wkh[t] += [(C_u* - C_t) is_u*t >= (L_u* - L_t) is_u*t],  u* = the u of S_t (lowest index of equals)
+// with is_ut = 1 / sigma_ut from launch_rell_pairsd (0 = the pair is excluded).  Every ratio is one rounded multiply of a rounded
+// difference.  A tree with no pair left counts every replicate.  The matrix is staged in dynamic LDS behind the table (LDS path)
+// or alone (global path) and read with wave-uniform ds_read_b128.
+struct RellWReq : RellReq {
+    const double *isig;             // [tpad][tpad] 1 / sigma_ut, symmetric, 0 on the diagonal, for excluded pairs and the padding
+    unsigned long long *wkh, *wsh;  // [T], zeroed by the caller
+};
 // rows of the LDS copy: tpad / 2 slots of 16 bytes rounded up to odd
 constexpr int rell_lds_slots(int tpad) { return (tpad / 2) | 1; }
 constexpr size_t rell_lds_bytes(int N, int tpad) { return (size_t)N * rell_lds_slots(tpad) * 16; }
@@ -234,6 +245,14 @@ void launch_rell_pack(const double *const *src /* device array of T device point
 hipError_t launch_rell(const RellReq &r, bool lds, hipStream_t s);
 // whether the LDS path can hold the table: the device's LDS per workgroup less the room kept for static LDS
 bool rell_lds_fits(int N, int tpad, int device);
+// isig[u][t] = isig[t][u] = 1 / sigma_ut for u < t < T, sigma_ut^2 = N / (N - 1) * sum_s (d_s - mean)^2 with d_s = X[s][u] - X[s][t]
+// and mean = (sum_s d_s) / N: two passes over the centred differences, plain f64, a fixed summation order (k_rell_pairsd: a
+// workgroup per 4 x 4 tile of pairs, its threads strided over the sites).  N = 1 or a zero sum of squares (identical columns)
+// gives 0; so do the diagonal and the padding column.  The whole [tpad][tpad] matrix is written.
+void launch_rell_pairsd(const double *X, double *isig, int N, int T, int tpad, hipStream_t s);
+// the weighted arm; lds as for launch_rell, after rell_weighted_lds_fits (table plus matrix)
+hipError_t launch_rell_weighted(const RellWReq &r, bool lds, hipStream_t s);
+bool rell_weighted_lds_fits(int N, int tpad, int device);
 
 // start / stop (launch_pmat, launch_oplist without ctl, launch_reduce; both or neither): timing events that the kernel's own
 // dispatch records its start and end in.  Unlike hipEventRecord before and after the launch this puts no marker packets into

@@ -1,10 +1,12 @@
-// treetest.cpp -- tree selection tests (include/peprml.h: pml_au_fit, pml_rell_tests, pml_tree_tests, pml_debug_rell):
+// treetest.cpp -- tree selection tests (include/peprml.h: pml_au_fit, pml_rell_tests, pml_tree_tests, pml_debug_rell, their
+// *_weighted forms and pml_catpv_table):
 // what TreeComparison.runConsel (TreeComparison.java:812-885) gets from `makermt -b 10 --puzzle | consel | catpv -v`.
 // The resampling and the counting run on the device (rell.hip); the host fits the AU curve to ten integers per tree.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <cstdio>
 #include <numeric>
 
 #include "../../include/peprml.h"
@@ -100,23 +102,42 @@ struct DevBuf {          // device allocations of one call, released together
 
 struct Scales { std::vector<double> r; std::vector<int> nk; int k1 = 0; };
 
+// what a weighted run (the weighted arm of k_rell) takes and gives on top of the plain one
+struct Weighted {
+    const double *isig_in = nullptr;        // host [T][T] 1 / sigma, or null: k_rell_pairsd
+    std::vector<double> isig;               // [T][T] the matrix that was used
+    std::vector<long long> wkh, wsh;        // [T]
+};
+
 // the resampling launch on a packed table: counts (and optionally every replicate sum and the kernel's HIP-event time) back
-// path: 0 = LDS when the table fits, 1 = LDS or PML_EINVAL, 2 = global
+// path: 0 = LDS when the table fits, 1 = LDS or PML_EINVAL, 2 = global;  w: null = the plain arm, exactly as ever
 int rell_run(Ctx &c, DevBuf &mem, const double *d_X, const double *d_L, int N, int T, const Scales &sc, long long B, unsigned long long seed,
-             int path, double *y_out, long long *bp, long long *kh, long long *sh, int *path_used, double *ms_out) {
+             int path, double *y_out, long long *bp, long long *kh, long long *sh, int *path_used, double *ms_out, Weighted *w = nullptr) {
     const int K = (int)sc.nk.size(), tpad = (T + 1) & ~1;
-    const bool fits = rell_lds_fits(N, tpad, c.device);
-    if (path == 1 && !fits) return c.fail(PML_EINVAL, "the table does not fit the LDS path");
+    const bool fits = w ? rell_weighted_lds_fits(N, tpad, c.device) : rell_lds_fits(N, tpad, c.device);
+    if (path == 1 && !fits) return c.fail(PML_EINVAL, w ? "the table and the 1 / sigma matrix do not fit the LDS path" : "the table does not fit the LDS path");
     bool lds = path == 2 ? false : fits;
-    int *d_nk = nullptr; double *d_scale = nullptr, *d_Y = nullptr; unsigned long long *d_cnt = nullptr;
-    const size_t ncnt = (size_t)K * T + 2 * (size_t)T;
+    int *d_nk = nullptr; double *d_scale = nullptr, *d_Y = nullptr, *d_isig = nullptr; unsigned long long *d_cnt = nullptr;
+    const size_t ncnt = (size_t)K * T + 2 * (size_t)T + (w ? 2 * (size_t)T : 0);
     std::vector<double> scale(K);
     for (int k = 0; k < K; ++k) scale[k] = (double)N / (double)sc.nk[k];
     TCHK(mem.get(&d_nk, K)); TCHK(mem.get(&d_scale, K)); TCHK(mem.get(&d_cnt, ncnt));
     if (y_out) TCHK(mem.get(&d_Y, (size_t)K * (size_t)B * T));
     TCHK(hipMemcpyAsync(d_nk, sc.nk.data(), sizeof(int) * K, hipMemcpyHostToDevice, c.stream));
     TCHK(hipMemcpyAsync(d_scale, scale.data(), sizeof(double) * K, hipMemcpyHostToDevice, c.stream));
-    RellReq r;
+    if (w) {
+        TCHK(mem.get(&d_isig, (size_t)tpad * tpad));
+        if (w->isig_in) {
+            std::vector<double> pad((size_t)tpad * tpad, 0.0);
+            for (int u = 0; u < T; ++u) for (int t = 0; t < T; ++t) pad[(size_t)u * tpad + t] = w->isig_in[(size_t)u * T + t];
+            TCHK(hipMemcpy(d_isig, pad.data(), sizeof(double) * pad.size(), hipMemcpyHostToDevice));
+        } else {
+            launch_rell_pairsd(d_X, d_isig, N, T, tpad, c.stream);
+            TCHK(hipGetLastError());
+        }
+    }
+    RellWReq r;
+    r.isig = d_isig; r.wkh = w ? d_cnt + (size_t)K * T + 2 * (size_t)T : nullptr; r.wsh = w ? r.wkh + T : nullptr;
     r.X = d_X; r.L = d_L; r.ndraws = d_nk; r.scale = d_scale; r.bp = d_cnt; r.kh = d_cnt + (size_t)K * T; r.sh = r.kh + T; r.Y = d_Y;
     r.base = (seed + 1ull) * 0x9E3779B97F4A7C15ull; r.B = (unsigned)B; r.N = N; r.T = T; r.tpad = tpad; r.K = K; r.k1 = sc.k1;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -125,7 +146,7 @@ int rell_run(Ctx &c, DevBuf &mem, const double *d_X, const double *d_L, int N, i
     for (;;) {
         TCHK(hipMemsetAsync(d_cnt, 0, ncnt * sizeof(unsigned long long), c.stream));
         if (ms_out) TCHK(hipEventRecord(ev0, c.stream));
-        const hipError_t e = launch_rell(r, lds, c.stream);
+        const hipError_t e = w ? launch_rell_weighted(r, lds, c.stream) : launch_rell(r, lds, c.stream);
         if (e != hipSuccess && lds && path == 0) { lds = false; continue; }       // the runtime refused the LDS size: global path, same bits
         if (e != hipSuccess && lds) return c.fail(PML_EINVAL, std::string("the runtime refused the LDS path: ") + hipGetErrorString(e));
         TCHK(e);
@@ -140,6 +161,13 @@ int rell_run(Ctx &c, DevBuf &mem, const double *d_X, const double *d_L, int N, i
     for (size_t i = 0; i < (size_t)K * T; ++i) bp[i] = (long long)cnt[i];
     for (int t = 0; t < T; ++t) { kh[t] = (long long)cnt[(size_t)K * T + t]; sh[t] = (long long)cnt[(size_t)K * T + T + t]; }
     if (y_out) TCHK(hipMemcpy(y_out, d_Y, sizeof(double) * (size_t)K * (size_t)B * T, hipMemcpyDeviceToHost));
+    if (w) {
+        w->wkh.resize(T); w->wsh.resize(T); w->isig.resize((size_t)T * T);
+        for (int t = 0; t < T; ++t) { w->wkh[t] = (long long)cnt[(size_t)K * T + 2 * (size_t)T + t]; w->wsh[t] = (long long)cnt[(size_t)K * T + 3 * (size_t)T + t]; }
+        std::vector<double> pad((size_t)tpad * tpad);
+        TCHK(hipMemcpy(pad.data(), d_isig, sizeof(double) * pad.size(), hipMemcpyDeviceToHost));
+        for (int u = 0; u < T; ++u) for (int t = 0; t < T; ++t) w->isig[(size_t)u * T + t] = pad[(size_t)u * tpad + t];
+    }
     if (path_used) *path_used = lds ? 1 : 2;
     return PML_OK;
 }
@@ -218,6 +246,42 @@ int fill_result(int N, int T, const Scales &sc, long long B, const double *L, co
     return PML_OK;
 }
 
+// counts + the matrix -> the weighted columns
+int fill_weighted(int T, long long B, const double *L, const Weighted &w, pml_tree_test_weighted *out) {
+    pml_tree_test_weighted &R = *out;
+    R.ntrees = T;
+    R.wkh = alloc_n<double>(T); R.wsh = alloc_n<double>(T); R.wkh_count = alloc_n<long long>(T); R.wsh_count = alloc_n<long long>(T);
+    R.sigma = alloc_n<double>((size_t)T * T); R.wkh_other = alloc_n<int>(T);
+    if (!R.wkh || !R.wsh || !R.wkh_count || !R.wsh_count || !R.sigma || !R.wkh_other) return PML_ENOMEM;
+    for (int t = 0; t < T; ++t) {
+        R.wkh_count[t] = w.wkh[t]; R.wsh_count[t] = w.wsh[t];
+        R.wkh[t] = (double)w.wkh[t] / (double)B; R.wsh[t] = (double)w.wsh[t] / (double)B;
+        // u* as the kernel chooses it: the same two rounded operations, the lowest index of equals
+        int us = -1; double S = -HUGE_VAL;
+        for (int u = 0; u < T; ++u) {
+            const double is = w.isig[(size_t)t * T + u];
+            R.sigma[(size_t)t * T + u] = is > 0.0 ? 1.0 / is : 0.0;
+            if (u == t || !(is > 0.0)) continue;
+            const double d = L[u] - L[t], q = d * is;
+            if (q > S) { S = q; us = u; }
+        }
+        R.wkh_other[t] = us;
+    }
+    return PML_OK;
+}
+
+// a caller's 1 / sigma matrix: finite, >= 0, symmetric, 0 on the diagonal
+bool isig_ok(const double *m, int T) {
+    for (int u = 0; u < T; ++u) {
+        if (m[(size_t)u * T + u] != 0.0) return false;
+        for (int t = 0; t < T; ++t) {
+            const double v = m[(size_t)u * T + t];
+            if (!std::isfinite(v) || v < 0.0 || v != m[(size_t)t * T + u]) return false;
+        }
+    }
+    return true;
+}
+
 bool shape_ok(long long N, int T) { return N >= 1 && N < 2147483648ll && T >= 2 && T <= 64; }
 
 }  // namespace
@@ -238,9 +302,9 @@ void pml_tree_test_result_free(pml_tree_test_result *R) {
     std::memset(R, 0, sizeof *R);
 }
 
-int pml_debug_rell(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws, long long reps,
-                   unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out, long long *sh_out, int *path_used,
-                   double *kernel_ms_out) {
+static int debug_rell(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws, long long reps,
+                      unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out, long long *sh_out, int *path_used,
+                      double *kernel_ms_out, Weighted *w) {
     if (!ctx || !site_lnl || !ndraws || !bp_out || !kh_out || !sh_out || !shape_ok(nsites, ntrees) || nscales <= 0 || reps <= 0 || path < 0 || path > 2)
         return PML_EINVAL;
     if ((unsigned long long)nscales * (unsigned long long)reps >= (1ull << 32)) return PML_EINVAL;
@@ -259,13 +323,37 @@ int pml_debug_rell(pml_ctx *ctx, long long nsites, int ntrees, const double *sit
         TCHK(hipSetDevice(c.device));
         DevBuf mem; double *d_X = nullptr, *d_L = nullptr;
         if (int rc = pack_host(c, mem, (int)nsites, ntrees, site_lnl, &d_X, &d_L)) return rc;
-        return rell_run(c, mem, d_X, d_L, (int)nsites, ntrees, sc, reps, seed, path, y_out, bp_out, kh_out, sh_out, path_used, kernel_ms_out);
+        return rell_run(c, mem, d_X, d_L, (int)nsites, ntrees, sc, reps, seed, path, y_out, bp_out, kh_out, sh_out, path_used, kernel_ms_out, w);
     } catch (const std::bad_alloc &) { return c.fail(PML_ENOMEM, "host allocation failed"); }
     catch (const std::exception &e) { return c.fail(PML_EINVAL, e.what()); }
 }
 
-int pml_rell_tests(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, const pml_tree_test_opts *opts, pml_tree_test_result *out) {
+int pml_debug_rell(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws, long long reps,
+                   unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out, long long *sh_out, int *path_used,
+                   double *kernel_ms_out) {
+    return debug_rell(ctx, nsites, ntrees, site_lnl, nscales, ndraws, reps, seed, path, y_out, bp_out, kh_out, sh_out, path_used, kernel_ms_out, nullptr);
+}
+
+int pml_debug_rell_weighted(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, int nscales, const long long *ndraws,
+                            long long reps, unsigned long long seed, int path, double *y_out, long long *bp_out, long long *kh_out,
+                            long long *sh_out, int *path_used, double *kernel_ms_out, const double *inv_sigma_in, double *inv_sigma_out,
+                            long long *wkh_out, long long *wsh_out) {
+    if (!ctx || !wkh_out || !wsh_out || !shape_ok(nsites, ntrees)) return PML_EINVAL;
+    if (inv_sigma_in && !isig_ok(inv_sigma_in, ntrees)) return PML_EINVAL;
+    try {
+        Weighted w; w.isig_in = inv_sigma_in;
+        const int rc = debug_rell(ctx, nsites, ntrees, site_lnl, nscales, ndraws, reps, seed, path, y_out, bp_out, kh_out, sh_out, path_used, kernel_ms_out, &w);
+        if (rc) return rc;
+        std::copy(w.wkh.begin(), w.wkh.end(), wkh_out); std::copy(w.wsh.begin(), w.wsh.end(), wsh_out);
+        if (inv_sigma_out) std::copy(w.isig.begin(), w.isig.end(), inv_sigma_out);
+        return PML_OK;
+    } catch (const std::exception &) { return PML_ENOMEM; }
+}
+
+static int rell_tests(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, const pml_tree_test_opts *opts, pml_tree_test_result *out,
+                      pml_tree_test_weighted *wout) {
     if (out) std::memset(out, 0, sizeof *out);
+    if (wout) std::memset(wout, 0, sizeof *wout);
     if (!ctx || !site_lnl || !out || !shape_ok(nsites, ntrees)) return PML_EINVAL;
     pml_fpguard fpg;
     std::lock_guard<std::mutex> lk(ctx->c.mu);
@@ -281,22 +369,35 @@ int pml_rell_tests(pml_ctx *ctx, long long nsites, int ntrees, const double *sit
         if ((rc = pack_host(c, mem, N, T, site_lnl, &d_X, &d_L))) return rc;
         std::vector<long long> bp((size_t)K * T), kh(T), sh(T); std::vector<double> L(T);
         TCHK(hipMemcpy(L.data(), d_L, sizeof(double) * T, hipMemcpyDeviceToHost));
-        rc = rell_run(c, mem, d_X, d_L, N, T, sc, B, opts ? opts->seed : 0ull, 0, nullptr, bp.data(), kh.data(), sh.data(), nullptr, nullptr);
+        Weighted w;
+        rc = rell_run(c, mem, d_X, d_L, N, T, sc, B, opts ? opts->seed : 0ull, 0, nullptr, bp.data(), kh.data(), sh.data(), nullptr, nullptr, wout ? &w : nullptr);
         if (!rc) rc = fill_result(N, T, sc, B, L.data(), nullptr, bp, kh, sh, out);
+        if (!rc && wout) rc = fill_weighted(T, B, L.data(), w, wout);
         if (rc == PML_ENOMEM) c.fail(rc, "allocation failed");
     } catch (const std::bad_alloc &) { rc = c.fail(PML_ENOMEM, "host allocation failed"); }
     catch (const std::exception &e) { rc = c.fail(PML_EINVAL, e.what()); }
-    if (rc) pml_tree_test_result_free(out);
+    if (rc) { pml_tree_test_result_free(out); pml_tree_test_weighted_free(wout); }
     return rc;
+}
+
+int pml_rell_tests(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, const pml_tree_test_opts *opts, pml_tree_test_result *out) {
+    return rell_tests(ctx, nsites, ntrees, site_lnl, opts, out, nullptr);
+}
+int pml_rell_tests_weighted(pml_ctx *ctx, long long nsites, int ntrees, const double *site_lnl, const pml_tree_test_opts *opts,
+                            pml_tree_test_result *out, pml_tree_test_weighted *wout) {
+    if (!wout) { if (out) std::memset(out, 0, sizeof *out); return PML_EINVAL; }
+    return rell_tests(ctx, nsites, ntrees, site_lnl, opts, out, wout);
 }
 
 // The T candidate trees are the genes of ONE batch (the same alignment in each), optimised together as `raxmlHPC -f g` optimises
 // each tree before it writes its per-site lnL; a gene's arithmetic does not depend on what shares its batch, so tree t carries
 // the numbers of a pml_optimize call on it alone.  The table is gathered from the per-pattern lnL the last evaluation left
 // in HBM: nothing but T scalars and the counts crosses the bus (plus the table itself when the caller asks for it).
-int pml_tree_tests(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const char *const *newicks, const pml_model *model,
-                   const pml_search_opts *search_opts, const pml_tree_test_opts *test_opts, pml_tree_test_result *out, double *site_lnl_out) {
+static int tree_tests(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const char *const *newicks, const pml_model *model,
+                      const pml_search_opts *search_opts, const pml_tree_test_opts *test_opts, pml_tree_test_result *out,
+                      pml_tree_test_weighted *wout, double *site_lnl_out) {
     if (out) std::memset(out, 0, sizeof *out);
+    if (wout) std::memset(wout, 0, sizeof *wout);
     if (!ctx || !aln || !newicks || !out || !shape_ok(aln->nsites, ntrees)) return PML_EINVAL;
     for (int t = 0; t < ntrees; ++t) if (!newicks[t]) return PML_EINVAL;
     pml_fpguard fpg;
@@ -335,18 +436,67 @@ int pml_tree_tests(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const cha
         TCHK(hipStreamSynchronize(c.stream));
         std::vector<long long> bp((size_t)K * T), kh(T), sh(T); std::vector<double> L(T);
         TCHK(hipMemcpy(L.data(), d_L, sizeof(double) * T, hipMemcpyDeviceToHost));
-        rc = rell_run(c, mem, d_X, d_L, N, T, sc, B, test_opts ? test_opts->seed : 0ull, 0, nullptr, bp.data(), kh.data(), sh.data(), nullptr, nullptr);
+        Weighted w;
+        rc = rell_run(c, mem, d_X, d_L, N, T, sc, B, test_opts ? test_opts->seed : 0ull, 0, nullptr, bp.data(), kh.data(), sh.data(), nullptr, nullptr,
+                      wout ? &w : nullptr);
         if (!rc && site_lnl_out) {                       // the very values that were resampled
             std::vector<double> X((size_t)N * tpad);
             TCHK(hipMemcpy(X.data(), d_X, sizeof(double) * X.size(), hipMemcpyDeviceToHost));
             for (int t = 0; t < T; ++t) for (int s = 0; s < N; ++s) site_lnl_out[(size_t)t * N + s] = X[(size_t)s * tpad + t];
         }
         if (!rc) rc = fill_result(N, T, sc, B, L.data(), lnl.data(), bp, kh, sh, out);
+        if (!rc && wout) rc = fill_weighted(T, B, L.data(), w, wout);
         if (rc == PML_ENOMEM) c.fail(rc, "allocation failed");
     } catch (const std::bad_alloc &) { rc = c.fail(PML_ENOMEM, "host allocation failed"); }
     catch (const std::exception &e) { rc = c.fail(PML_EINVAL, e.what()); }
-    if (rc) pml_tree_test_result_free(out);
+    if (rc) { pml_tree_test_result_free(out); pml_tree_test_weighted_free(wout); }
     return rc;
+}
+
+int pml_tree_tests(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const char *const *newicks, const pml_model *model,
+                   const pml_search_opts *search_opts, const pml_tree_test_opts *test_opts, pml_tree_test_result *out, double *site_lnl_out) {
+    return tree_tests(ctx, aln, ntrees, newicks, model, search_opts, test_opts, out, nullptr, site_lnl_out);
+}
+int pml_tree_tests_weighted(pml_ctx *ctx, const pml_alignment *aln, int ntrees, const char *const *newicks, const pml_model *model,
+                            const pml_search_opts *search_opts, const pml_tree_test_opts *test_opts, pml_tree_test_result *out,
+                            pml_tree_test_weighted *wout, double *site_lnl_out) {
+    if (!wout) { if (out) std::memset(out, 0, sizeof *out); return PML_EINVAL; }
+    return tree_tests(ctx, aln, ntrees, newicks, model, search_opts, test_opts, out, wout, site_lnl_out);
+}
+
+void pml_tree_test_weighted_free(pml_tree_test_weighted *R) {
+    if (!R) return;
+    void *p[] = {R->wkh, R->wsh, R->wkh_count, R->wsh_count, R->sigma, R->wkh_other};
+    for (void *q : p) std::free(q);
+    std::memset(R, 0, sizeof *R);
+}
+
+int pml_catpv_table(const pml_tree_test_result *r, const pml_tree_test_weighted *w, char **out) {
+    if (out) *out = nullptr;
+    if (!r || !out || r->ntrees < 1 || !r->rank || !r->obs || !r->au || !r->np || !r->bp || !r->pp || !r->kh || !r->sh) return PML_EINVAL;
+    if (w && (w->ntrees != r->ntrees || !w->wkh || !w->wsh)) return PML_EINVAL;
+    try {
+        const int T = r->ntrees;
+        std::vector<int> order(T);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return r->rank[x] < r->rank[y]; });
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "# %4s %4s %8s %6s %6s | %6s %6s %6s %6s %6s %6s |", "rank", "item", "obs", "au", "np", "bp", "pp", "kh", "sh", "wkh", "wsh");
+        std::string txt = buf;
+        for (int t : order) {
+            std::snprintf(buf, sizeof buf, "\n# %4d %4d %8.1f %6.3f %6.3f | %6.3f %6.3f %6.3f %6.3f", r->rank[t], t + 1, r->obs[t], r->au[t], r->np[t], r->bp[t],
+                          r->pp[t], r->kh[t], r->sh[t]);
+            txt += buf;
+            if (w) std::snprintf(buf, sizeof buf, " %6.3f %6.3f |", w->wkh[t], w->wsh[t]);
+            else std::snprintf(buf, sizeof buf, " %6s %6s |", "-", "-");
+            txt += buf;
+        }
+        char *p = (char *)std::malloc(txt.size() + 1);
+        if (!p) return PML_ENOMEM;
+        std::memcpy(p, txt.c_str(), txt.size() + 1);
+        *out = p;
+        return PML_OK;
+    } catch (const std::exception &) { return PML_ENOMEM; }
 }
 
 }  // extern "C"

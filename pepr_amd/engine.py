@@ -361,27 +361,43 @@ class Context:
             out[f] = arr(getattr(res, f), T, np.float64)
         return out
 
-    def rell_tests(self, site_lnl, scales=None, reps=10000, seed=0):
+    def _weighted_result(self, w):
+        T = w.ntrees
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True)
+        return {"wkh": arr(w.wkh, T, np.float64), "wsh": arr(w.wsh, T, np.float64), "wkh_count": arr(w.wkh_count, T, np.int64),
+                "wsh_count": arr(w.wsh_count, T, np.int64), "sigma": arr(w.sigma, T * T, np.float64).reshape(T, T),
+                "wkh_other": arr(w.wkh_other, T, np.int64)}
+
+    def rell_tests(self, site_lnl, scales=None, reps=10000, seed=0, weighted=False):
         """AU / KH / SH / BP of T trees from their per-site lnL (T x N, the rows of RAxML_perSiteLLs): multiscale RELL on the
         device.  scales None = 0.5 ... 1.4; reps per scale (PEPR's `makermt -b 10`: 100000).  -> dict of per-tree arrays
-        (lnl, obs, au, np, bp, kh, sh, pp, au_d, au_c, au_rss, au_nused, rank) and the raw counts bp_count[K, T], kh_count, sh_count."""
+        (lnl, obs, au, np, bp, kh, sh, pp, au_d, au_c, au_rss, au_nused, rank) and the raw counts bp_count[K, T], kh_count, sh_count.
+        weighted=True (pml_rell_tests_weighted): the same values plus wkh, wsh, wkh_count, wsh_count, sigma[T, T], wkh_other."""
         x = np.ascontiguousarray(site_lnl, dtype=np.float64)
         if x.ndim != 2:
             raise ValueError("site_lnl must be trees x sites")
         keep = []
         o = self._test_opts(scales, reps, seed, keep)
-        res = _lib.TreeTestResult()
-        rc = self.L.pml_rell_tests(self.ptr, x.shape[1], x.shape[0], _dp(x), C.byref(o), C.byref(res))
+        res, w = _lib.TreeTestResult(), _lib.TreeTestWeighted()
+        if weighted:
+            rc = self.L.pml_rell_tests_weighted(self.ptr, x.shape[1], x.shape[0], _dp(x), C.byref(o), C.byref(res), C.byref(w))
+        else:
+            rc = self.L.pml_rell_tests(self.ptr, x.shape[1], x.shape[0], _dp(x), C.byref(o), C.byref(res))
         self._check(rc)
         out = self._test_result(res)
         self.L.pml_tree_test_result_free(C.byref(res))
+        if weighted:
+            out.update(self._weighted_result(w))
+            self.L.pml_tree_test_weighted_free(C.byref(w))
         return out
 
     def tree_tests(self, gene, newicks, alpha=1.0, ncat=4, pi_mode=PI_RAXML_3DP, optimize=True, optimize_alpha=True, epsilon=1e-4,
-                   scales=None, reps=10000, seed=0):
+                   scales=None, reps=10000, seed=0, weighted=False):
         """The whole runConsel chain for one alignment and T candidate trees in one call: every tree optimised (optimize=False:
         scored as given) in one device batch, the per-site lnL table built and resampled on the device.  -> the dict of
-        rell_tests plus "site_lnl" (T x N, the very values that were resampled)."""
+        rell_tests plus "site_lnl" (T x N, the very values that were resampled); weighted=True adds the keys rell_tests adds."""
         keep = []
         a = _aln_struct(gene[0], gene[1], keep)
         T = len(newicks)
@@ -389,18 +405,27 @@ class Context:
         m = _model(ncat, alpha, pi_mode)
         so = _opts(optimize_alpha, False, 0, epsilon)
         o = self._test_opts(scales, reps, seed, keep)
-        res = _lib.TreeTestResult()
+        res, w = _lib.TreeTestResult(), _lib.TreeTestWeighted()
         site = np.zeros((T, max(a.nsites, 1)))
-        rc = self.L.pml_tree_tests(self.ptr, C.byref(a), T, nw, C.byref(m), C.byref(so) if optimize else None, C.byref(o), C.byref(res), _dp(site))
+        if weighted:
+            rc = self.L.pml_tree_tests_weighted(self.ptr, C.byref(a), T, nw, C.byref(m), C.byref(so) if optimize else None, C.byref(o), C.byref(res),
+                                                C.byref(w), _dp(site))
+        else:
+            rc = self.L.pml_tree_tests(self.ptr, C.byref(a), T, nw, C.byref(m), C.byref(so) if optimize else None, C.byref(o), C.byref(res), _dp(site))
         self._check(rc)
         out = self._test_result(res)
         self.L.pml_tree_test_result_free(C.byref(res))
+        if weighted:
+            out.update(self._weighted_result(w))
+            self.L.pml_tree_test_weighted_free(C.byref(w))
         out["site_lnl"] = site[:, :a.nsites]
         return out
 
-    def debug_rell(self, site_lnl, ndraws, reps, seed=0, path=0, want_y=True):
+    def debug_rell(self, site_lnl, ndraws, reps, seed=0, path=0, want_y=True, weighted=False, inv_sigma=None):
         """Test door of k_rell: scale k draws ndraws[k] sites.  path 0 = auto, 1 = LDS, 2 = global memory.
-        -> {"Y": [K, reps, T] replicate sums (None unless want_y), "bp": [K, T], "kh": [T], "sh": [T], "path": 1 | 2, "ms": kernel time}"""
+        -> {"Y": [K, reps, T] replicate sums (None unless want_y), "bp": [K, T], "kh": [T], "sh": [T], "path": 1 | 2, "ms": kernel time}
+        weighted=True (or an inv_sigma matrix [T, T]): the weighted arm through pml_debug_rell_weighted, with inv_sigma None
+        computed by k_rell_pairsd; adds "wkh", "wsh" [T] and "inv_sigma" [T, T], the matrix that was used."""
         x = np.ascontiguousarray(site_lnl, dtype=np.float64)
         T, N = x.shape
         nd = np.ascontiguousarray(ndraws, dtype=np.int64)
@@ -409,10 +434,21 @@ class Context:
         y = np.zeros((K, reps, T)) if want_y else None
         bp, kh, sh = np.zeros((K, T), dtype=np.int64), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
         used, ms = C.c_int(0), C.c_double(0)
-        rc = self.L.pml_debug_rell(self.ptr, N, T, _dp(x), K, nd.ctypes.data_as(lp), int(reps), int(seed), int(path), _dp(y) if want_y else None,
-                                   bp.ctypes.data_as(lp), kh.ctypes.data_as(lp), sh.ctypes.data_as(lp), C.byref(used), C.byref(ms))
+        if not weighted and inv_sigma is None:
+            rc = self.L.pml_debug_rell(self.ptr, N, T, _dp(x), K, nd.ctypes.data_as(lp), int(reps), int(seed), int(path), _dp(y) if want_y else None,
+                                       bp.ctypes.data_as(lp), kh.ctypes.data_as(lp), sh.ctypes.data_as(lp), C.byref(used), C.byref(ms))
+            self._check(rc)
+            return {"Y": y, "bp": bp, "kh": kh, "sh": sh, "path": used.value, "ms": ms.value}
+        isin = None if inv_sigma is None else np.ascontiguousarray(inv_sigma, dtype=np.float64)
+        if isin is not None and isin.shape != (T, T):
+            raise ValueError("inv_sigma must be trees x trees")
+        isout, wkh, wsh = np.zeros((T, T)), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
+        rc = self.L.pml_debug_rell_weighted(self.ptr, N, T, _dp(x), K, nd.ctypes.data_as(lp), int(reps), int(seed), int(path),
+                                            _dp(y) if want_y else None, bp.ctypes.data_as(lp), kh.ctypes.data_as(lp), sh.ctypes.data_as(lp),
+                                            C.byref(used), C.byref(ms), _dp(isin) if isin is not None else None, _dp(isout),
+                                            wkh.ctypes.data_as(lp), wsh.ctypes.data_as(lp))
         self._check(rc)
-        return {"Y": y, "bp": bp, "kh": kh, "sh": sh, "path": used.value, "ms": ms.value}
+        return {"Y": y, "bp": bp, "kh": kh, "sh": sh, "path": used.value, "ms": ms.value, "wkh": wkh, "wsh": wsh, "inv_sigma": isout}
 
     def newton_fallbacks(self):
         """how often k_newton's bounded exchange wait gave up on this context and work was re-issued through the no-exchange form"""
@@ -517,6 +553,40 @@ class Batch:
         s = C.string_at(p).decode()
         self.L.pml_free(p)
         return s
+
+
+def catpv_table(result, weighted=None):
+    """Host-only (pml_catpv_table): the lines of the `catpv -v`-shaped table -- a header and one line per tree in rank order,
+    columns rank item obs au np | bp pp kh sh wkh wsh | -- from a result dict of rell_tests / tree_tests.  weighted: None = the
+    result's own wkh / wsh if it has them (else the two columns print "-"), or a dict that holds them."""
+    L = _lib.load()
+    T = int(result["ntrees"])
+    keep = {f: np.ascontiguousarray(result[f], dtype=np.float64) for f in ("obs", "au", "np", "bp", "pp", "kh", "sh")}
+    rank = np.ascontiguousarray(result["rank"], dtype=np.int32)
+    res = _lib.TreeTestResult()
+    res.ntrees = T
+    res.rank = rank.ctypes.data_as(C.POINTER(C.c_int))
+    for f, a in keep.items():
+        if a.shape != (T,):
+            raise ValueError(f + " must hold one value per tree")
+        setattr(res, f, _dp(a))
+    if rank.shape != (T,):
+        raise ValueError("rank must hold one value per tree")
+    wsrc = weighted if weighted is not None else (result if "wkh" in result and "wsh" in result else None)
+    w, wp = _lib.TreeTestWeighted(), None
+    if wsrc is not None:
+        wk, ws = (np.ascontiguousarray(wsrc[f], dtype=np.float64) for f in ("wkh", "wsh"))
+        if wk.shape != (T,) or ws.shape != (T,):
+            raise ValueError("wkh / wsh must hold one value per tree")
+        w.ntrees, w.wkh, w.wsh = T, _dp(wk), _dp(ws)
+        wp = C.byref(w)
+    out = C.c_void_p()
+    rc = L.pml_catpv_table(C.byref(res), wp, C.byref(out))
+    if rc != 0:
+        raise PmlError(rc, "pml_catpv_table")
+    txt = C.string_at(out).decode()
+    L.pml_free(out)
+    return txt.split("\n")
 
 
 def au_fit(r, count, B):

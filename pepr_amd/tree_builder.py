@@ -263,26 +263,29 @@ class FastTreeRunner:
 
 class TreeComparison:
     """.../pepr/tree/TreeComparison.java:812-885 runConsel: `raxmlHPC -f g` on the trees, then `makermt -b 10 --puzzle`, `consel`
-    and `catpv -v` on its per-site lnL -- here one engine call (pml_tree_tests).  Not built: the weighted tests wKH / wSH
-    (catpv -v prints them after sh; the columns are left out, not filled with something else)."""
+    and `catpv -v` on its per-site lnL -- here one engine call (pml_tree_tests, or pml_tree_tests_weighted).  weighted=True returns
+    the whole table of `catpv -v`, the weighted tests wKH / wSH after sh; the default leaves the two columns out, as ever."""
 
     REPS = 100000          # makermt's 10 000 replicates per scale times the -b 10 of the reference's command line
 
-    def __init__(self, ctx=None, reps=None, seed=0):
-        self.ctx, self.reps, self.seed = ctx, reps or self.REPS, seed
+    def __init__(self, ctx=None, reps=None, seed=0, weighted=False):
+        self.ctx, self.reps, self.seed, self.weighted = ctx, reps or self.REPS, seed, weighted
         self.result = None
 
     def runConsel(self, alignment, trees, processors=None, matrix="PROTGAMMAWAG"):
         """alignment: SequenceAlignment; trees: Newick strings; processors is accepted and ignored; matrix is resolved as
         RAxMLRunner resolves it (an unbuilt model name raises before anything touches a device).
         -> the lines of a `catpv -v`-shaped table, one row per tree sorted by rank (item = 1-based index into trees):
-           # rank item obs au np | bp pp kh sh |"""
+           # rank item obs au np | bp pp kh sh |            or, weighted (the lines of pml_catpv_table),
+           # rank item obs au np | bp pp kh sh wkh wsh |"""
         mdl = _model_from_matrix(matrix, self.ctx)
         ctx = self.ctx or default_context()
-        r = ctx.tree_tests(alignment.as_gene(), [str(t) for t in trees], reps=self.reps, seed=self.seed, **mdl)
+        r = ctx.tree_tests(alignment.as_gene(), [str(t) for t in trees], reps=self.reps, seed=self.seed, weighted=self.weighted, **mdl)
         self.result = r
-        lines = ["# reading per-site lnL of %d trees x %d sites, %d scales x %d replicates" % (r["ntrees"], r["nsites"], r["nscales"], r["reps"]),
-                 "# %4s %4s %8s %6s %6s | %6s %6s %6s %6s |" % ("rank", "item", "obs", "au", "np", "bp", "pp", "kh", "sh")]
+        lines = ["# reading per-site lnL of %d trees x %d sites, %d scales x %d replicates" % (r["ntrees"], r["nsites"], r["nscales"], r["reps"])]
+        if self.weighted:
+            return lines + engine.catpv_table(r)
+        lines.append("# %4s %4s %8s %6s %6s | %6s %6s %6s %6s |" % ("rank", "item", "obs", "au", "np", "bp", "pp", "kh", "sh"))
         for t in sorted(range(r["ntrees"]), key=lambda i: r["rank"][i]):
             lines.append("# %4d %4d %8.1f %6.3f %6.3f | %6.3f %6.3f %6.3f %6.3f |" % (
                 r["rank"][t], t + 1, r["obs"][t], r["au"][t], r["np"][t], r["bp"][t], r["pp"][t], r["kh"][t], r["sh"][t]))
