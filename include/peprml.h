@@ -159,7 +159,7 @@ void pml_result_free(pml_result *r);
  * pml_matrix_register stores a matrix on the context and returns its model code (see PML_PI_REGISTERED); the frequencies
  * are normalised to sum 1.  Registering a name again replaces nothing, it returns a new code.  Thread-safe like every
  * context call.  Codes are accepted wherever PML_PI_EMPIRICAL is; pml_jackknife takes the own-frequency codes only and
- * refuses "F" codes and PML_PI_GTR at entry.
+ * refuses "F" codes and PML_PI_GTR at entry (pml_jackknife2 takes them all).
  * pml_model_eval is the reference's -matrix_eval loop (PhylogenomicPipeline2.java:1390-1452, getTreeScore :1482-1500) as ONE
  * device batch: the tree is optimised (branch lengths, alpha if opts says so, rates where the code is PML_PI_GTR) under each
  * of the nmodels codes; out[i] is what pml_optimize returns under codes[i] (4 categories, start alpha 1), bit for bit;
@@ -223,6 +223,45 @@ typedef struct {
 int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *model,
                   const pml_jackknife_opts *opts, pml_result *main_out /* newick carries the supports */,
                   char **support_newicks_out /* optional: reps lines, '\n'-separated; pml_free */);
+/* The same loop with the model the pipeline chose and with the decorator's counts:
+ *   models    every valid pi_mode for the full tree (full_model) and for the support trees (support_model, NULL = the full
+ *             tree's): the shared codes, PML_PI_EMPIRICAL, PML_PI_GTR, registered codes and registered + 1.  `-matrix_eval`
+ *             hands mlMatrix to the full tree (PhylogenomicPipeline2.java:855-858) and to every gene-subset tree (:1247,
+ *             :1619-1620); with FastTree supports (the default, :335-338) those stay WAG while the full tree uses mlMatrix.
+ *             A replicate exists only as a code matrix in HBM, so a per-gene code gets its frequencies from a histogram of
+ *             that matrix counted on the device (k_codehist): PML_PI_EMPIRICAL decomposes WAG with them, registered + 1 goes
+ *             through the model-build kernel, PML_PI_GTR starts from WAG with them and estimates its rates as in any batch.
+ *   counts    support_rule, applied to the support trees AS RETURNED in support_newicks_out:
+ *             PML_SUPPORT_EQUAL_TAXA  pml_jackknife's rule: a replicate that lacks a taxon of the full tree supports nothing
+ *             PML_SUPPORT_DECORATOR   TreeSupportDecorator.addSupportValues (:86-163) on those strings: every node of every
+ *                       support tree, as its text roots it (after unroot()), adds Bipartition(its leaves found among the main
+ *                       tree's sorted taxa, main taxon count) -- complement over the MAIN taxa, smaller side by cardinality, on
+ *                       a tie the side holding the lowest index (Bipartition.java:41-64) -- to a multiset; a main branch gets
+ *                       the multiset count of its own bipartition.  What a Java caller gets from decorating the strings; it
+ *                       depends on where a subset tree's text is rooted.
+ *             PML_SUPPORT_RESTRICTED  a replicate with taxon set S supports the main split A|B if A&S and B&S hold at least
+ *                       two taxa each and the replicate has the split A&S | B&S: independent of any rooting
+ *             For replicates over the main tree's taxon set the three rules agree.
+ * base has pml_jackknife's meaning (draw, sub-batching by free HBM, sharding).  With support_model NULL, rule 0 and a shared
+ * code the call returns pml_jackknife's strings. */
+enum { PML_SUPPORT_EQUAL_TAXA = 0, PML_SUPPORT_DECORATOR = 1, PML_SUPPORT_RESTRICTED = 2 };
+typedef struct {
+    pml_jackknife_opts base;
+    const pml_model *support_model;   /* NULL = the full tree's model */
+    int support_rule;                 /* PML_SUPPORT_* */
+} pml_jackknife_opts2;
+int pml_jackknife2(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *full_model,
+                   const pml_jackknife_opts2 *opts, pml_result *main_out, char **support_newicks_out);
+/* host-only: pml_support_tree under one of the PML_SUPPORT_* rules; support trees may cover other taxon sets than the main
+ * tree's (rule 0 counts such a tree as not supporting, where pml_support_tree returns PML_EPARSE) */
+int pml_support_tree_rule(const char *main_newick, int ntrees, const char *const *support_newicks, int rule, int digits,
+                          char **out);
+/* test hook for k_codehist, as pml_debug_gather is for k_gather: gathers the selection `sel` (NULL = all genes) on the device
+ * in one batch with the replicate of all genes, counts both code matrices in one launch and reads the selection's result
+ * back: counts_out[code] = the number of cells (taxon x site, absent taxa = gap cells) holding the code, pi_out = the
+ * empirical frequencies of the "F" scheme from those counts */
+int pml_debug_replicate_freqs(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nsel, const int *sel,
+                              long long counts_out[23], double pi_out[20]);
 /* host-only: the gene subsets pml_jackknife draws for (ngenes, reps, subset_size, seed) -- replicate r = sel_out[r*k .. r*k+k),
  * ascending gene indices, k = the return value (subset_size, or ngenes/2 when 0; < 0 = error).  The reference draws them with
  * RandomSetUtils.getRandomSet (.../pepr/util/RandomSetUtils.java:9-35, unseeded java.util.Random); callers that need to know
@@ -417,7 +456,8 @@ int pml_debug_fpenv(unsigned *values, int cap);
 enum { PML_K_PMAT = 0, PML_K_NEWVIEW = 1, PML_K_EVALUATE = 2, PML_K_SUMTABLE = 3, PML_K_NEWTON = 4,
        PML_K_REDUCE = 5,
        PML_K_HOST_BUILD = 6 /* CPU ms building descriptors */, PML_K_HOST_WAIT = 7 /* CPU ms in stream sync */,
-       PML_K_MODEL = 8 /* model builds (k_model): eigen-systems of per-gene and registered rate matrices */, PML_K_COUNT = 9 };
+       PML_K_MODEL = 8 /* model builds (k_model): eigen-systems of per-gene and registered rate matrices */, 
+       PML_K_CODEHIST = 9 /* code histograms of device-gathered replicates (k_codehist); bytes = code-matrix bytes read */, PML_K_COUNT = 10 };
 int pml_kernel_stats(pml_ctx *ctx, int kernel, long long *launches, double *total_ms,
                      double *algo_bytes /* algorithmic bytes moved, SURVEY 8d figures */);
 /* algorithmic flops of the launches counted by pml_kernel_stats, SURVEY 8d's per-operation figures (newview inner-inner 6480,

@@ -22,6 +22,7 @@ SYMBOLS = [
     "pml_matrix_parse_paml", "pml_matrix_register", "pml_model_eval", "pml_batch_set_matrix", "pml_batch_get_matrix", "pml_debug_model_build", "pml_newton_fallbacks", "pml_sh_support", "pml_sh_support_batch", "pml_gamma20", "pml_gamma20_batch", "pml_debug_fpenv", "pml_kernel_stats", "pml_kernel_flops", "pml_kernel_stats_reset",
     "pml_au_fit", "pml_rell_tests", "pml_tree_tests", "pml_tree_test_result_free", "pml_debug_rell",
     "pml_rell_tests_weighted", "pml_tree_tests_weighted", "pml_tree_test_weighted_free", "pml_debug_rell_weighted", "pml_catpv_table",
+    "pml_jackknife2", "pml_support_tree_rule", "pml_debug_replicate_freqs",
 ]
 
 
@@ -49,6 +50,10 @@ class JackknifeOpts(C.Structure):
     _fields_ = [("reps", C.c_int), ("subset_size", C.c_int), ("seed", C.c_ulonglong),
                 ("spr_radius_full", C.c_int), ("epsilon", C.c_double),
                 ("shard_rank", C.c_int), ("shard_world", C.c_int)]
+
+
+class JackknifeOpts2(C.Structure):
+    _fields_ = [("base", JackknifeOpts), ("support_model", C.POINTER(Model)), ("support_rule", C.c_int)]
 
 
 class ParsimonyOpts(C.Structure):
@@ -131,6 +136,9 @@ def load():
     L.pml_jackknife.argtypes = [vp, C.c_int, ap, mp, C.POINTER(JackknifeOpts), rp, C.POINTER(vp)]
     L.pml_jackknife_draw.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ulonglong, ip]
     L.pml_debug_gather.argtypes = [vp, C.c_int, ap, C.c_int, ip, ip, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.pml_jackknife2.argtypes = [vp, C.c_int, ap, mp, C.POINTER(JackknifeOpts2), rp, C.POINTER(vp)]
+    L.pml_support_tree_rule.argtypes = [C.c_char_p, C.c_int, cpp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.pml_debug_replicate_freqs.argtypes = [vp, C.c_int, ap, C.c_int, ip, C.POINTER(C.c_longlong), dp]
     L.pml_parsimony.argtypes = [vp, ap, C.POINTER(ParsimonyOpts), rp, C.POINTER(C.c_longlong)]
     L.pml_parsimony_batch.argtypes = [vp, C.c_int, ap, C.POINTER(ParsimonyOpts), rp, C.POINTER(C.c_longlong)]
     L.pml_refine_next.argtypes = [C.c_char_p, C.c_int, C.c_int, cpp, C.POINTER(vp), ip, C.POINTER(vp)]

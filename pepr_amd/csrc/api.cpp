@@ -602,6 +602,22 @@ int pml_support_tree(const char *main_newick, int ntrees, const char *const *sup
     return *out ? PML_OK : PML_ENOMEM;
 }
 
+int pml_support_tree_rule(const char *main_newick, int ntrees, const char *const *support, int rule, int digits, char **out) {
+    if (!main_newick || !out || ntrees < 0 || (ntrees > 0 && !support)) return PML_EINVAL;
+    *out = nullptr;
+    if (rule != PML_SUPPORT_EQUAL_TAXA && rule != PML_SUPPORT_DECORATOR && rule != PML_SUPPORT_RESTRICTED) { g_err = "bad support rule " + std::to_string(rule); return PML_EINVAL; }
+    try {
+        std::vector<std::string> names; Tree main; std::string err;
+        if (!Tree::parse_free(main_newick, names, main, err)) { g_err = err; return PML_EPARSE; }
+        std::vector<const char *> sup(support, support + ntrees);
+        for (int i = 0; i < ntrees; ++i) if (!sup[i]) { g_err = "support tree " + std::to_string(i) + ": null newick"; return PML_EPARSE; }
+        std::vector<std::vector<int>> counts;
+        if (!support_counts_rule(main, names, sup, rule, counts, err)) { g_err = err; return PML_EPARSE; }
+        *out = dup_string(main.newick_labeled(names, digits, counts));
+    } catch (const std::exception &e) { g_err = e.what(); return PML_EINVAL; }
+    return *out ? PML_OK : PML_ENOMEM;
+}
+
 int pml_sh_support_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char *const *newicks, const pml_model *model,
                          int nboot, unsigned long long seed, pml_result *out) {
     if (!ctx || !alns || !newicks || !out || n <= 0 || nboot <= 0) return PML_EINVAL;

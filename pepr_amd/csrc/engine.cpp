@@ -148,13 +148,17 @@ int Batch::alloc_gene_models() {
     HIPCHK(hipHostMalloc((void **)&h_mreq, n * sizeof(ModelReq), hipHostMallocDefault));
     return 0;
 }
+void Batch::empirical_pi(int g, double *pi) const {
+    if (genes[g].counted_pi.empty()) empirical_freqs(genes[g].aln, pi);
+    else std::memcpy(pi, genes[g].counted_pi.data(), sizeof(double) * NS);
+}
 void Batch::matrix_for(int g, double *exch, double *pi) const {
     const int code = genes[g].model_code;
     const Matrix *M = ctx->matrix_of(code);
     std::memcpy(exch, M ? M->exch : wag_exch(), sizeof(double) * NEXCH);
     // GTR starts from WAG in the scale the estimates are reported in: the last exchangeability, which stays fixed, is 1
     if (code == PM_GTR) { const double last = exch[NEXCH - 1]; for (int i = 0; i < NEXCH; ++i) exch[i] /= last; }
-    if (model_per_gene(code)) empirical_freqs(genes[g].aln, pi);
+    if (model_per_gene(code)) empirical_pi(g, pi);
     else std::memcpy(pi, M ? M->pi : wag_pi(code), sizeof(double) * NS);
     double sum = 0;
     for (int i = 0; i < NS; ++i) sum += pi[i];
@@ -172,7 +176,7 @@ int Batch::build_gene_models() {
         const int code = genes[g].model_code;
         if (code == 2) {
             double pi[NS];
-            empirical_freqs(genes[g].aln, pi);
+            empirical_pi(g, pi);
             Model m; m.init_pi(pi);
             fill_model_dev(m, h[g]);
             std::memcpy(h_gexch + (size_t)g * NEXCH, wag_exch(), sizeof(double) * NEXCH); std::memcpy(h_gpi + (size_t)g * NS, m.pi, sizeof m.pi);
@@ -538,11 +542,12 @@ int Batch::create_replicates(Ctx *c, const GeneStore &store, const std::vector<s
     virtual_pitch = virtual_cherries && std::getenv("PML_NO_PITCH") == nullptr;
     const int n = (int)sel.size();
     if (n <= 0) return ctx->fail(-1, "empty batch");
-    if (model_per_gene(pm)) return ctx->fail(-1, ctx->model_name(pm) + " (a model per gene: empirical frequencies or estimated rates) is built for score / optimize / search calls, not for device-gathered replicates");
-    if (int rc = ctx->ensure_model(pm)) return rc;
-    d_shared = ctx->shared_of(pm)->d_model; d_shared_eig = ctx->shared_of(pm)->d_eigfrags;
+    if (int rc = ctx->ensure_model(pm)) return rc;                 // also refuses an unknown code
+    const bool per_gene = model_per_gene(pm);
+    if (!per_gene) { d_shared = ctx->shared_of(pm)->d_model; d_shared_eig = ctx->shared_of(pm)->d_eigfrags; }
     HIPCHK(hipSetDevice(ctx->device));
     genes.resize(n);
+    for (auto &G : genes) G.model_code = pm;
     struct SegH { int rep, gene, off; size_t rowmap_off; };
     std::vector<SegH> segs; std::vector<int> rowmaps;
     int max_npat = 0;
@@ -597,6 +602,42 @@ int Batch::create_replicates(Ctx *c, const GeneStore &store, const std::vector<s
     hipError_t e3 = ctx->sync(ctx->stream) ? hipErrorUnknown : hipSuccess;
     hipFree(d_buf);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return ctx->fail(-4, "replicate gather failed");
+    if (!per_gene) return 0;
+    // a model per replicate, as Batch::create builds one per gene: the frequencies come from the gathered matrix itself
+    if (int rc = count_replicate_freqs()) return rc;
+    return build_gene_models();
+}
+
+int Batch::count_replicate_freqs() {
+    const int n = (int)genes.size();
+    const size_t req_bytes = align_up((size_t)n * sizeof(CodeHistReq), 256), out_bytes = (size_t)n * NCODES * sizeof(long long);
+    std::vector<CodeHistReq> hr((size_t)n);
+    std::vector<long long> hist((size_t)n * NCODES);
+    int max_mpad = 0;
+    for (int g = 0; g < n; ++g) { const Gene &G = genes[g]; hr[g] = CodeHistReq{G.d_codes, G.d_weight, G.aln.ntax, G.aln.mpad}; max_mpad = std::max(max_mpad, G.aln.mpad); }
+    char *d_buf = nullptr;
+    HIPCHK(hipMalloc((void **)&d_buf, req_bytes + out_bytes));
+    long long *d_out = (long long *)(d_buf + req_bytes);
+    size_t cells = 0;
+    for (auto &G : genes) cells += (size_t)G.aln.ntax * G.aln.mpad;
+    hipError_t e = hipMemcpyAsync(d_buf, hr.data(), (size_t)n * sizeof(CodeHistReq), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, out_bytes, ctx->stream);
+    if (e == hipSuccess) {
+        ctx->tic(K_CODEHIST, (double)cells);
+        launch_codehist((const CodeHistReq *)d_buf, n, max_mpad, d_out, ctx->stream);
+        ctx->toc();
+        e = hipMemcpyAsync(hist.data(), d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess && ctx->sync(ctx->stream)) e = hipErrorUnknown;
+    if (e == hipSuccess) e = hipGetLastError();
+    hipFree(d_buf);
+    if (e != hipSuccess) return ctx->fail(-4, std::string("code histogram of the replicates failed: ") + hipGetErrorString(e));
+    for (int g = 0; g < n; ++g) {
+        Gene &G = genes[g];
+        G.code_hist.assign(hist.begin() + (size_t)g * NCODES, hist.begin() + (size_t)(g + 1) * NCODES);
+        G.counted_pi.resize(NS);
+        empirical_freqs_from_counts(G.code_hist.data(), G.counted_pi.data());
+    }
     return 0;
 }
 

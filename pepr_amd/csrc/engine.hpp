@@ -14,7 +14,7 @@ namespace pml {
 
 constexpr int MAXTAIL = 4;            // tail requests (evaluate / sumtable+Newton) per gene per run()
 
-enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_COUNT = 9 };
+enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_CODEHIST = 9, K_COUNT = 10 };
 
 // Model codes (pml_model.pi_mode): 0 / 1 WAG with fixed frequencies, 2 WAG with the gene's empirical frequencies, 3 GTR
 // (exchangeabilities estimated per gene, empirical frequencies), 16 + 2 i the i-th registered matrix with its own
@@ -80,6 +80,9 @@ struct Gene {
     double rates[NCAT] = {1, 1, 1, 1};
     unsigned rates_epoch = 0;      // bumped by set_alpha (cached score plans refresh a gene's rates only when it moved)
     int model_code = 0;            // pml_model.pi_mode of this gene (pml_model_eval: one batch, a code per gene)
+    // device-gathered replicates under a per-gene code: the weighted histogram of the 23 codes (k_codehist) and the empirical
+    // frequencies it gives; empty for genes encoded from text, whose frequencies are counted by empirical_freqs
+    std::vector<long long> code_hist; std::vector<double> counted_pi;
     // device pointers (inside the batch arena)
     uint8_t *d_codes = nullptr;
     double *d_weight = nullptr;
@@ -143,6 +146,8 @@ struct Batch {
     int build_gene_models();
     // the exchangeabilities and (normalised) frequencies gene g's code stands for (empirical frequencies counted from its alignment)
     void matrix_for(int g, double *exch190, double *pi20) const;
+    void empirical_pi(int g, double *pi20) const;       // gene g's counted frequencies: from its text, or from its device histogram
+    int count_replicate_freqs();                        // k_codehist over every gene of a gathered batch -> code_hist, counted_pi
     // k_model + k_eigfrags for the listed genes from d_gexch / d_gpi; patch >= 0: rate `patch` of gene gs[i] counts as vals[i]
     int build_models(const std::vector<int> &gs, int patch, const double *vals);
     int set_matrix(int g /* -1 = all */, const double *exch190, const double *pi20 /* null = keep */);
@@ -227,7 +232,8 @@ struct Batch {
                int pi_mode, int ncat, double alpha, bool score_only, const int *gene_codes = nullptr /* a code per gene instead of pi_mode */);
     // one batch gene per replicate = the concatenation of the selected store genes (sorted taxon union, absent
     // taxa = gap rows, MSAConcatenator rules); code matrices are gathered on the device, NJ start trees come from
-    // the summed pair counts: no column text is touched again
+    // the summed pair counts: no column text is touched again.  A per-gene code (empirical frequencies, GTR) gives every
+    // replicate its own model, its frequencies counted on the device (k_codehist)
     int create_replicates(Ctx *c, const GeneStore &store, const std::vector<std::vector<int>> &sel, int pi_mode, int ncat, double alpha);
     int layout(double alpha, bool score_only);
     void destroy();

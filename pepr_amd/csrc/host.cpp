@@ -8,6 +8,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
+#include <set>
 #include <unordered_map>
 
 namespace pml {
@@ -195,6 +197,18 @@ int aa_code(int ch) {
 }
 
 static unsigned host_code_mask(int code) { return code < 20 ? (1u << code) : (code == 20 ? 0xCu : (code == 21 ? 0x60u : 0xFFFFFu)); }
+// the floor both counts end with: frequencies below 0.001 are lifted to it, the others scaled down to keep the sum
+static void floor_freqs(const double *counted, double *pi) {
+    double f[20];
+    for (int l = 0; l < 20; ++l) f[l] = counted[l];
+    for (int round = 0; round < 100; ++round) {
+        double lift = 0.0, big = 0.0; int low = 0;
+        for (int l = 0; l < 20; ++l) { if (f[l] < 0.001) { lift += 0.001 - f[l]; ++low; } else big += f[l]; }
+        if (!low) break;
+        for (int l = 0; l < 20; ++l) f[l] = f[l] < 0.001 ? 0.001 : f[l] * (1.0 - lift / big);
+    }
+    for (int l = 0; l < 20; ++l) pi[l] = f[l];
+}
 // PROTGAMMAWAGF: eight sweeps of proportional counting from 1/20, then a floor of 0.001 (oracle: po_empirical_freqs)
 void empirical_freqs(const EncodedAlignment &a, double *pi) {
     double f[20], acc[20];
@@ -212,13 +226,29 @@ void empirical_freqs(const EncodedAlignment &a, double *pi) {
         for (int l = 0; l < 20; ++l) tot += acc[l];
         for (int l = 0; l < 20; ++l) f[l] = acc[l] / tot;
     }
-    for (int round = 0; round < 100; ++round) {
-        double lift = 0.0, big = 0.0; int low = 0;
-        for (int l = 0; l < 20; ++l) { if (f[l] < 0.001) { lift += 0.001 - f[l]; ++low; } else big += f[l]; }
-        if (!low) break;
-        for (int l = 0; l < 20; ++l) f[l] = f[l] < 0.001 ? 0.001 : f[l] * (1.0 - lift / big);
+    floor_freqs(f, pi);
+}
+// every (taxon, pattern) cell of code c adds weight / sum * f[l] in a sweep: cells of one code add the same term, so a
+// sweep needs hist[c] = the summed weights of the cells holding c, nothing else.  Same eight sweeps, same floor; the
+// text path above keeps its own summation order (and its bits).
+void empirical_freqs_from_counts(const long long *hist, double *pi) {
+    double f[20], acc[20];
+    for (int l = 0; l < 20; ++l) f[l] = 0.05;
+    for (int sweep = 0; sweep < 8; ++sweep) {
+        for (int l = 0; l < 20; ++l) acc[l] = 0.0;
+        for (int c = 0; c < 23; ++c) {
+            if (hist[c] == 0) continue;
+            const unsigned mk = host_code_mask(c);
+            double sum = 0.0;
+            for (int l = 0; l < 20; ++l) if ((mk >> l) & 1) sum += f[l];
+            const double wj = (double)hist[c] / sum;
+            for (int l = 0; l < 20; ++l) if ((mk >> l) & 1) acc[l] += wj * f[l];
+        }
+        double tot = 0.0;
+        for (int l = 0; l < 20; ++l) tot += acc[l];
+        for (int l = 0; l < 20; ++l) f[l] = acc[l] / tot;
     }
-    for (int l = 0; l < 20; ++l) pi[l] = f[l];
+    floor_freqs(f, pi);
 }
 
 bool EncodedAlignment::encode(int nt, int ns, const char *const *nm, const char *const *rows, std::string &err) {
@@ -445,6 +475,100 @@ std::vector<std::vector<int>> support_counts(const Tree &main, const std::vector
         counts[u][main.slot(u, v)] = c[i]; counts[v][main.slot(v, u)] = c[i];
     }
     return counts;
+}
+
+// Leaf sets of every node of a support tree as its text roots it, over main's taxa (bit = rank of the name among main's
+// sorted names; leaves main lacks set nothing).  unroot: BasicTree.unroot() first -- a two-child root hands its second child
+// to the first (to the second when the first is a leaf) and stays behind childless, with an empty set.
+static bool rooted_leaf_sets(const char *newick, const std::unordered_map<std::string, int> &rank, int words, bool unroot,
+                             std::vector<std::vector<uint64_t>> &sets, int &root_out, std::string &err) {
+    if (!newick) { err = "null newick"; return false; }
+    Parser P{newick};
+    const int root = P.subtree(0);
+    if (root < 0) { err = P.err; return false; }
+    const int n = (int)P.nodes.size();
+    std::vector<char> leaf((size_t)n);
+    for (int v = 0; v < n; ++v) leaf[v] = P.nodes[v].kids.empty();
+    root_out = root;
+    if (unroot && P.nodes[root].kids.size() == 2) {
+        int np = P.nodes[root].kids[0], nc = P.nodes[root].kids[1];
+        if (P.nodes[np].kids.size() < 2) std::swap(np, nc);
+        P.nodes[np].kids.push_back(nc); leaf[np] = 0;
+        P.nodes[root].kids.clear();
+        root_out = np;
+    }
+    sets.assign((size_t)n, std::vector<uint64_t>((size_t)words, 0));
+    for (int v = 0; v < n; ++v) if (leaf[v]) { auto it = rank.find(P.nodes[v].label); if (it != rank.end()) sets[v][it->second >> 6] |= 1ULL << (it->second & 63); }
+    std::vector<int> order;                                       // parents before children; folded in reverse
+    std::vector<char> seen((size_t)n, 0);
+    for (int start : {root, root_out}) {
+        if (seen[start]) continue;
+        std::vector<int> stack{start};
+        while (!stack.empty()) { const int v = stack.back(); stack.pop_back(); seen[v] = 1; order.push_back(v); for (int c : P.nodes[v].kids) stack.push_back(c); }
+    }
+    std::vector<int> parent((size_t)n, -1);
+    for (int v = 0; v < n; ++v) for (int c : P.nodes[v].kids) parent[c] = v;
+    for (size_t i = order.size(); i-- > 0;) { const int v = order[i], p = parent[v]; if (p >= 0) for (int w = 0; w < words; ++w) sets[p][w] |= sets[v][w]; }
+    return true;
+}
+
+bool support_counts_rule(const Tree &main, const std::vector<std::string> &names, const std::vector<const char *> &support, int rule,
+                         std::vector<std::vector<int>> &counts, std::string &err) {
+    if (rule == SUPPORT_EQUAL_TAXA) {
+        std::vector<Tree> usable;
+        for (size_t i = 0; i < support.size(); ++i) {
+            std::vector<std::string> nm; Tree t; std::string e;
+            if (!Tree::parse_free(support[i], nm, t, e)) { err = "support tree " + std::to_string(i) + ": " + e; return false; }
+            if (Tree::parse(support[i], names, t, e)) usable.push_back(t);        // any other taxon set: counted as not supporting
+        }
+        counts = support_counts(main, usable);
+        return true;
+    }
+    if (rule != SUPPORT_DECORATOR && rule != SUPPORT_RESTRICTED) { err = "bad support rule " + std::to_string(rule); return false; }
+    const int n = main.ntax, words = (n + 63) / 64;
+    std::vector<int> by_name((size_t)n);                           // Arrays.sort on the leaf labels: code-unit order
+    for (int i = 0; i < n; ++i) by_name[i] = i;
+    std::sort(by_name.begin(), by_name.end(), [&](int a, int b) { return names[a] < names[b]; });
+    std::vector<int> rank_of((size_t)n);
+    std::unordered_map<std::string, int> rank;
+    for (int r = 0; r < n; ++r) { rank_of[by_name[r]] = r; rank[names[by_name[r]]] = r; }
+    auto card = [&](const std::vector<uint64_t> &s) { int c = 0; for (uint64_t w : s) c += __builtin_popcountll(w); return c; };
+    std::vector<uint64_t> all((size_t)words, 0);
+    for (int r = 0; r < n; ++r) all[r >> 6] |= 1ULL << (r & 63);
+    // Bipartition(bipart, size): the smaller side; equal cardinalities: the side whose lowest set bit is lower, i.e. index 0's
+    auto smaller_side = [&](std::vector<uint64_t> s) {
+        const int c = card(s);
+        if (2 * c > n || (2 * c == n && !(s[0] & 1))) for (int w = 0; w < words; ++w) s[w] = all[w] & ~s[w];
+        return s;
+    };
+    std::vector<std::vector<uint64_t>> tips, ms; std::vector<std::pair<int, int>> edges;
+    collect_splits(main, tips, &edges);
+    for (auto &s : tips) {
+        std::vector<uint64_t> r((size_t)words, 0);
+        for (int i = 0; i < n; ++i) if ((s[i >> 6] >> (i & 63)) & 1) r[rank_of[i] >> 6] |= 1ULL << (rank_of[i] & 63);
+        ms.push_back(r);
+    }
+    std::vector<int> c(ms.size(), 0);
+    std::map<std::vector<uint64_t>, int> multiset;
+    for (size_t t = 0; t < support.size(); ++t) {
+        std::vector<std::vector<uint64_t>> sets; int root = 0; std::string e;
+        if (!rooted_leaf_sets(support[t], rank, words, rule == SUPPORT_DECORATOR, sets, root, e)) { err = "support tree " + std::to_string(t) + ": " + e; return false; }
+        if (rule == SUPPORT_DECORATOR) { for (auto &s : sets) ++multiset[smaller_side(s)]; continue; }
+        const std::vector<uint64_t> S = sets[root];
+        std::set<std::vector<uint64_t>> has(sets.begin(), sets.end());
+        for (size_t i = 0; i < ms.size(); ++i) {
+            std::vector<uint64_t> a(S), b(S);
+            for (int w = 0; w < words; ++w) { a[w] &= ms[i][w]; b[w] &= ~ms[i][w]; }
+            if (card(a) >= 2 && card(b) >= 2 && (has.count(a) || has.count(b))) ++c[i];
+        }
+    }
+    if (rule == SUPPORT_DECORATOR) for (size_t i = 0; i < ms.size(); ++i) { auto it = multiset.find(smaller_side(ms[i])); c[i] = it == multiset.end() ? 0 : it->second; }
+    counts.assign(main.nnodes(), std::vector<int>(3, -1));
+    for (size_t i = 0; i < ms.size(); ++i) {
+        const int u = edges[i].first, v = edges[i].second;
+        counts[u][main.slot(u, v)] = c[i]; counts[v][main.slot(v, u)] = c[i];
+    }
+    return true;
 }
 
 std::string Tree::newick_labeled(const std::vector<std::string> &names, int digits, const std::vector<std::vector<int>> &lab) const {

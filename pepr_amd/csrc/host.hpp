@@ -29,6 +29,9 @@ bool parse_paml(const char *text, double *exch190, double *pi20, std::string &er
 struct EncodedAlignment;
 // empirical amino-acid frequencies, RAxML's "F" models (spec: oracle/pml_oracle.c po_empirical_freqs)
 void empirical_freqs(const EncodedAlignment &a, double *pi20);
+// the same scheme from the weighted histogram of the 23 codes alone (every sweep is a function of hist[code]): what a
+// device-gathered replicate, whose code matrix exists only in HBM, is counted with (freq.hip k_codehist)
+void empirical_freqs_from_counts(const long long *hist23, double *pi20);
 
 // mean rates of K equal-probability Gamma(alpha, mean 1) bins (Yang 1994); K==1 -> {1}
 void gamma_rates(double alpha, int K, double *rates);
@@ -58,6 +61,19 @@ struct Tree {
 int rf_distance(const Tree &a, const Tree &b);    // (|A|+|B|-2|A&B|)/2 over non-trivial splits
 // counts[u][k] = number of `others` containing the bipartition of main's internal edge (u, nbr[u][k]); -1 elsewhere
 std::vector<std::vector<int>> support_counts(const Tree &main, const std::vector<Tree> &others);
+// The same table from support trees given as Newick TEXT that may cover other taxon sets than main's, under one of three rules:
+//   SUPPORT_EQUAL_TAXA  a tree counts only if its leaf set is main's (pml_jackknife's rule; any other tree supports nothing)
+//   SUPPORT_DECORATOR   TreeSupportDecorator.addSupportValues (:86-163) on these strings: every node of every support tree,
+//                       as rooted in its text after BasicTree.unroot() (:669-717), adds Bipartition(descendant leaves found
+//                       among main's sorted taxa, taxon count) (Bipartition.java:41-64: complement over MAIN's taxa, smaller
+//                       side by cardinality, on a tie the side holding the lowest index) to a multiset; an edge's count is
+//                       the multiset count of its own bipartition.  Depends on where a subset tree's text is rooted.
+//   SUPPORT_RESTRICTED  a tree with taxon set S supports main's split A|B if A&S and B&S hold >= 2 taxa each and the tree has
+//                       the split A&S | B&S: independent of the rooting of any text
+// For trees over main's taxon set the three rules give the same counts.  false + err: a support text does not parse.
+enum { SUPPORT_EQUAL_TAXA = 0, SUPPORT_DECORATOR = 1, SUPPORT_RESTRICTED = 2 };
+bool support_counts_rule(const Tree &main, const std::vector<std::string> &main_names, const std::vector<const char *> &support,
+                         int rule, std::vector<std::vector<int>> &counts, std::string &err);
 
 // PhylogeneticTreeRefiner.getNextIndexToRefine / AdvancedTree.getMeanDescendantSupportValues on a rooted
 // support-labelled Newick: ingroup = comma-joined sorted leaves of the next clade to refine ("" = none);

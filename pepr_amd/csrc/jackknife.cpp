@@ -4,6 +4,8 @@
 // union of the genes' taxon names, a gene that lacks a taxon contributes '?' columns.
 // Gene alignments are encoded once into HBM; the full alignment and every replicate are gathered from them on
 // the device (GeneStore / Batch::create_replicates) and the replicates are searched as ONE batch; the support counting is TreeSupportDecorator.addSupportValues (:86-163).
+// pml_jackknife2 is the same loop under any model code (a model per replicate, its frequencies counted on the device by
+// k_codehist), with another model for the support trees and the counting rules of host.hpp support_counts_rule.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -118,9 +120,10 @@ extern "C" int pml_debug_gather(pml_ctx *ctx, int ngenes, const pml_alignment *g
     return PML_OK;
 }
 
-extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *model,
-                             const pml_jackknife_opts *opts, pml_result *main_out, char **support_out) {
-    if (!ctx || !genes || ngenes <= 0 || !main_out) return PML_EINVAL;
+// The loop itself, for pml_jackknife (one shared-model code, SUPPORT_EQUAL_TAXA) and pml_jackknife2 (any valid code for the
+// full tree and for the support trees, any counting rule).  The caller holds the context's mutex and has checked the codes.
+static int jackknife_run(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *model, const pml_model *support_model,
+                         int rule, const pml_jackknife_opts *opts, pml_result *main_out, char **support_out) {
     pml_fpguard fpg;
     std::memset(main_out, 0, sizeof *main_out);
     if (support_out) *support_out = nullptr;
@@ -132,13 +135,6 @@ extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *gene
     if (reps < 0) return PML_EINVAL;
     const int sworld = (opts && opts->shard_world > 1) ? opts->shard_world : 1, srank = sworld > 1 ? opts->shard_rank : 0;
     if (srank < 0 || srank >= sworld) return PML_EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->c.mu);
-    // a replicate is a device-side concatenation of genes: it has no alignment text to count frequencies from and no matrix
-    // of its own, so the per-gene models are refused here, before anything is encoded or uploaded
-    if (model && !ctx->c.valid_code(model->pi_mode)) return ctx->c.fail(PML_EINVAL, "bad pi_mode " + std::to_string(model->pi_mode));
-    if (model && model_per_gene(model->pi_mode))
-        return ctx->c.fail(PML_EINVAL, ctx->c.model_name(model->pi_mode) + " is not available for the gene-wise jackknife: its replicates are gathered on the device and "
-                                       "carry one shared model (use PROTGAMMAWAG or a registered matrix with its own frequencies)");
     pml_drop_worker_caches(ctx);
     try {
         std::vector<int> all(ngenes); for (int i = 0; i < ngenes; ++i) all[i] = i;
@@ -159,6 +155,9 @@ extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *gene
         const int reps_here = (int)rep.size();
         const int ncat = model ? model->ncat : 4, pm = model ? model->pi_mode : 0;
         const double alpha = model ? model->alpha : 1.0;
+        // the support trees' model (FastTree supports stay WAG while the full tree uses mlMatrix, PhylogenomicPipeline2.java:335-338)
+        const int sncat = support_model ? support_model->ncat : 4, spm = support_model ? support_model->pi_mode : 0;
+        const double salpha = support_model ? support_model->alpha : 1.0;
         // full tree
         Tree main_tree; std::vector<std::string> main_names; double main_lnl = 0, main_alpha = alpha; int main_npat = 0, main_nsites = 0;
         if (srank == 0) {
@@ -187,7 +186,7 @@ extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *gene
                 size_t used = 0; int end = begin;
                 while (end < reps_here) { const size_t need = rep_bytes(rep[end]); if (end > begin && used + need > budget) break; used += need; ++end; }
                 std::vector<std::vector<int>> part(rep.begin() + begin, rep.begin() + end);
-                Batch b; int rc = b.create_replicates(&ctx->c, store, part, pm, ncat, alpha);
+                Batch b; int rc = b.create_replicates(&ctx->c, store, part, spm, sncat, salpha);
                 std::vector<double> l(end - begin);
                 if (!rc) rc = b.search(true, 0, true, eps, l.data());
                 if (rc) { b.destroy(); return rc; }
@@ -197,7 +196,7 @@ extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *gene
                     sup_txt += nw; sup_txt += '\n';
                     // a replicate may lack taxa that occur only in unselected genes: such trees cannot
                     // contain the main tree's bipartitions and are counted as not supporting
-                    if (srank != 0) continue;
+                    if (srank != 0 || rule != SUPPORT_EQUAL_TAXA) continue;
                     if (G.aln.names == main_names) sup[r] = G.tree;
                     else { std::string e2; Tree t; if (Tree::parse(nw.c_str(), main_names, t, e2)) sup[r] = t; else sup[r] = Tree(); }
                 }
@@ -207,12 +206,78 @@ extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *gene
         }
         std::vector<Tree> usable;
         for (auto &t : sup) if (t.ntax == main_tree.ntax) usable.push_back(t);
-        const std::string out = srank == 0 ? main_tree.newick_labeled(main_names, 6, support_counts(main_tree, usable)) : std::string();
+        std::vector<std::vector<int>> counts;
+        if (srank == 0 && rule == SUPPORT_EQUAL_TAXA) counts = support_counts(main_tree, usable);
+        else if (srank == 0) {             // the other rules read the support trees as the caller will: the returned strings
+            std::vector<std::string> lines; std::vector<const char *> ptrs; std::string err;
+            for (size_t b = 0, e; b < sup_txt.size(); b = e + 1) { e = sup_txt.find('\n', b); lines.push_back(sup_txt.substr(b, e - b)); }
+            for (auto &l : lines) ptrs.push_back(l.c_str());
+            if (!support_counts_rule(main_tree, main_names, ptrs, rule, counts, err)) return ctx->c.fail(PML_EPARSE, err);
+        }
+        const std::string out = srank == 0 ? main_tree.newick_labeled(main_names, 6, counts) : std::string();
         main_out->lnl = main_lnl; main_out->alpha = main_alpha; main_out->tree_length = main_tree.length();
         main_out->npatterns = main_npat; main_out->nsites = main_nsites;
         if (srank == 0) main_out->newick = dup_cstr(out);
         if (support_out) *support_out = dup_cstr(sup_txt);
         if (srank == 0 && !main_out->newick) return ctx->c.fail(PML_ENOMEM, "host allocation failed");
+    } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+    catch (const std::exception &e) { return ctx->c.fail(PML_EINVAL, e.what()); }
+    return PML_OK;
+}
+
+extern "C" int pml_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *model,
+                             const pml_jackknife_opts *opts, pml_result *main_out, char **support_out) {
+    if (!ctx || !genes || ngenes <= 0 || !main_out) return PML_EINVAL;
+    std::memset(main_out, 0, sizeof *main_out);
+    if (support_out) *support_out = nullptr;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    // this entry keeps one shared model for the full tree and the replicates: the per-gene codes are refused here, before
+    // anything is encoded or uploaded (pml_jackknife2 builds a model per replicate)
+    if (model && !ctx->c.valid_code(model->pi_mode)) return ctx->c.fail(PML_EINVAL, "bad pi_mode " + std::to_string(model->pi_mode));
+    if (model && model_per_gene(model->pi_mode))
+        return ctx->c.fail(PML_EINVAL, ctx->c.model_name(model->pi_mode) + " is not available for the gene-wise jackknife: its replicates are gathered on the device and "
+                                       "carry one shared model (use PROTGAMMAWAG or a registered matrix with its own frequencies)");
+    return jackknife_run(ctx, ngenes, genes, model, model, SUPPORT_EQUAL_TAXA, opts, main_out, support_out);
+}
+
+extern "C" int pml_jackknife2(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *full_model,
+                              const pml_jackknife_opts2 *opts, pml_result *main_out, char **support_out) {
+    if (!ctx || !genes || ngenes <= 0 || !main_out) return PML_EINVAL;
+    std::memset(main_out, 0, sizeof *main_out);
+    if (support_out) *support_out = nullptr;
+    const int rule = opts ? opts->support_rule : PML_SUPPORT_EQUAL_TAXA;
+    const pml_model *sm = (opts && opts->support_model) ? opts->support_model : full_model;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    if (rule != PML_SUPPORT_EQUAL_TAXA && rule != PML_SUPPORT_DECORATOR && rule != PML_SUPPORT_RESTRICTED) return ctx->c.fail(PML_EINVAL, "bad support_rule " + std::to_string(rule));
+    for (const pml_model *m : {full_model, sm}) {
+        if (m && !ctx->c.valid_code(m->pi_mode)) return ctx->c.fail(PML_EINVAL, "bad pi_mode " + std::to_string(m->pi_mode));
+        if (m && m->ncat != 1 && m->ncat != 4) return ctx->c.fail(PML_EINVAL, "ncat must be 1 or 4");
+    }
+    return jackknife_run(ctx, ngenes, genes, full_model, sm, rule, opts ? &opts->base : nullptr, main_out, support_out);
+}
+
+// Test hook for k_codehist: the selection is gathered TOGETHER with the replicate of all genes (one batch, one k_codehist
+// launch over two replicates that may differ in taxa and patterns) and its histogram and frequencies are read back.
+extern "C" int pml_debug_replicate_freqs(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nsel, const int *sel,
+                                         long long counts_out[23], double pi_out[20]) {
+    if (!ctx || !genes || ngenes <= 0 || !counts_out || !pi_out || (sel && nsel <= 0)) return PML_EINVAL;
+    pml_fpguard fpg;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    pml_drop_worker_caches(ctx);
+    try {
+        for (int g = 0; g < ngenes; ++g) if (!genes[g].names || !genes[g].rows || genes[g].ntax <= 0) return ctx->c.fail(PML_EINVAL, "bad alignment");
+        std::vector<int> all(ngenes); for (int i = 0; i < ngenes; ++i) all[i] = i;
+        std::vector<std::vector<int>> reps{all};
+        if (sel) reps.emplace_back(sel, sel + nsel);
+        GeneStore store;
+        struct Drop { GeneStore &s; ~Drop() { s.destroy(); } } drop{store};
+        if (int rc = store.create(&ctx->c, ngenes, reinterpret_cast<const pml_alignment_view *>(genes))) return rc;
+        Batch b;
+        struct DropB { Batch &b; ~DropB() { b.destroy(); } } dropb{b};
+        if (int rc = b.create_replicates(&ctx->c, store, reps, PML_PI_EMPIRICAL, 4, 1.0)) return rc;
+        const Gene &G = b.genes.back();
+        std::copy(G.code_hist.begin(), G.code_hist.end(), counts_out);
+        std::copy(G.counted_pi.begin(), G.counted_pi.end(), pi_out);
     } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
     catch (const std::exception &e) { return ctx->c.fail(PML_EINVAL, e.what()); }
     return PML_OK;

@@ -181,6 +181,10 @@ struct GatherSeg {
     int src_mpad, npat, dst_mpad, dst_off, ntax_dst, pad;
 };
 void launch_gather(const GatherSeg *segs, int nsegs, int max_npat, hipStream_t s);
+// freq.hip k_codehist: out[r][code] += the summed weights (integers stored as f64) of the cells of replicate r's code matrix
+// that hold `code`; one launch for all replicates, `out` (nreqs x NCODES, 64-bit integers) zeroed by the caller
+struct CodeHistReq { const uint8_t *codes; const double *weight; int ntax, mpad; };
+void launch_codehist(const CodeHistReq *reqs, int nreqs, int max_mpad, long long *out, hipStream_t s);
 
 // SH-like local support of one split (FastTree's SHSupport; Guindon et al. 2010): per-pattern lnL of the current
 // arrangement (l0) and of its two NNI alternatives (l1, l2); nboot resamples of nsites alignment columns drawn with

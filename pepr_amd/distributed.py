@@ -108,18 +108,24 @@ def gather_results(gene_ids, lnl, alpha=None, tree_length=None, newicks=None, ne
     return out
 
 
-def jackknife(ctx, genes, reps=100, seed=0, newick_bytes=None, **kw):
+def jackknife(ctx, genes, reps=100, seed=0, newick_bytes=None, support_rule=None, support_pi_mode=None, **kw):
     """Gene-wise jackknife over all ranks (PhylogenomicPipeline2.java:994-1126 across GPUs): rank r searches the
     replicates r, r+world, ... (pml_jackknife_opts.shard_*; every rank draws the same subsets from `seed`), rank 0
     also searches the full tree; ONE gather of the support trees, then the supports are counted on rank 0.
     A rank whose engine call fails still joins the gather (status < 0 in its records) so that nobody hangs; the
-    failure is then raised on that rank and on rank 0.  Returns the single-GPU result dict on rank 0, None elsewhere."""
+    failure is then raised on that rank and on rank 0.  Returns the single-GPU result dict on rank 0, None elsewhere.
+    support_rule / support_pi_mode (both None: the default path, Context.jackknife): the loop through Context.jackknife2 --
+    any model code, another code for the support trees, and the gathered trees counted under that SUPPORT_* rule."""
     from . import engine
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     err = None
     try:
-        part = ctx.jackknife(genes, reps=reps, seed=seed, shard=(rank, world), **kw)
+        if support_rule is None and support_pi_mode is None:
+            part = ctx.jackknife(genes, reps=reps, seed=seed, shard=(rank, world), **kw)
+        else:
+            part = ctx.jackknife2(genes, reps=reps, seed=seed, shard=(rank, world), support_rule=support_rule or 0,
+                                  support_pi_mode=support_pi_mode, **kw)
     except Exception as e:              # noqa: BLE001 -- reported through the gather, re-raised below
         if world == 1:
             raise
@@ -144,6 +150,9 @@ def jackknife(ctx, genes, reps=100, seed=0, newick_bytes=None, **kw):
     import re
     plain = re.sub(r"\)\d+:", "):", part["newick"])
     part["support_trees"] = sup
+    if support_rule is not None or support_pi_mode is not None:
+        part["newick"] = engine.support_tree_rule(plain, sup, rule=support_rule or 0, digits=6)
+        return part
     leaves = lambda t: sorted(re.findall(r"[(,]([^(),:;]+)", t))
     # a replicate that lacks taxa of the full tree cannot contain its bipartitions (counted as not supporting)
     part["newick"] = engine.support_tree(plain, [t for t in sup if t and leaves(t) == leaves(plain)], digits=6)

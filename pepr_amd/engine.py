@@ -9,8 +9,9 @@ import numpy as np
 from . import _lib
 
 KERNELS = {"pmat": 0, "newview": 1, "evaluate": 2, "sumtable": 3, "newton": 4, "reduce": 5,
-           "host_build": 6, "host_wait": 7, "model": 8}
+           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9}
 PI_RAXML_3DP, PI_WAG_FULL, PI_EMPIRICAL = 0, 1, 2      # PI_EMPIRICAL = PROTGAMMAWAGF (frequencies counted per gene)
+SUPPORT_EQUAL_TAXA, SUPPORT_DECORATOR, SUPPORT_RESTRICTED = 0, 1, 2      # pml_jackknife2 / pml_support_tree_rule counting rules
 PI_GTR = 3             # PROTGAMMAGTR: exchangeabilities estimated per gene by the optimising calls, empirical frequencies
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
@@ -246,6 +247,45 @@ class Context:
         if sup:
             self.L.pml_free(sup)
         return out
+
+    def jackknife2(self, genes, reps=100, subset_size=0, seed=0, spr_radius_full=5, epsilon=1e-3, alpha=1.0, ncat=4,
+                   pi_mode=PI_RAXML_3DP, support_pi_mode=None, support_alpha=None, support_rule=SUPPORT_EQUAL_TAXA, shard=(0, 1)):
+        """jackknife() under any model code (per-gene codes too: every replicate gets its own model, its frequencies counted
+        on the device), optionally another code for the support trees (support_pi_mode; None = the full tree's), and one of
+        the SUPPORT_* counting rules (1 = what TreeSupportDecorator.addSupportValues gives on the returned strings)."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        m = _model(ncat, alpha, pi_mode)
+        sm = None
+        if support_pi_mode is not None or support_alpha is not None:
+            sm = _model(ncat, alpha if support_alpha is None else support_alpha, pi_mode if support_pi_mode is None else support_pi_mode)
+        o = _lib.JackknifeOpts2(_lib.JackknifeOpts(reps, subset_size, seed, spr_radius_full, epsilon, int(shard[0]), int(shard[1])),
+                                C.pointer(sm) if sm is not None else None, int(support_rule))
+        res = _lib.Result()
+        sup = C.c_void_p()
+        rc = self.L.pml_jackknife2(self.ptr, n, alns, C.byref(m), C.byref(o), C.byref(res), C.byref(sup))
+        self._check(rc)
+        out = {"lnl": res.lnl, "alpha": res.alpha, "tree_length": res.tree_length, "npatterns": res.npatterns,
+               "nsites": res.nsites, "newick": C.string_at(res.newick).decode() if res.newick else None,
+               "support_trees": C.string_at(sup).decode().splitlines() if sup else []}
+        self.L.pml_result_free(C.byref(res))
+        if sup:
+            self.L.pml_free(sup)
+        return out
+
+    def debug_replicate_freqs(self, genes, sel=None):
+        """Test hook for k_codehist: the code histogram of the device-gathered selection (None = all genes) and the empirical
+        frequencies counted from it -> (counts int64[23], pi float64[20])."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        counts, pi = np.zeros(23, dtype=np.int64), np.zeros(20)
+        arr = (C.c_int * len(sel))(*sel) if sel is not None else None
+        rc = self.L.pml_debug_replicate_freqs(self.ptr, n, alns, len(sel) if sel is not None else 0, arr,
+                                              counts.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(pi))
+        self._check(rc)
+        return counts, pi
 
     def debug_gather(self, genes, sel=None):
         """Test hook: the replicate code matrix k_gather builds on the device for the gene selection,
@@ -650,6 +690,20 @@ def support_tree(main_newick, support_newicks, digits=6):
     arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in support_newicks]) if n else None
     p = C.c_void_p()
     rc = L.pml_support_tree(main_newick.encode(), n, arr, digits, C.byref(p))
+    if rc:
+        raise PmlError(rc, L.pml_last_error(None).decode())
+    s = C.string_at(p).decode()
+    L.pml_free(p)
+    return s
+
+
+def support_tree_rule(main_newick, support_newicks, rule=SUPPORT_DECORATOR, digits=6):
+    """support_tree() under a SUPPORT_* rule; the support trees may cover other taxon sets than the main tree's."""
+    L = _lib.load()
+    n = len(support_newicks)
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in support_newicks]) if n else None
+    p = C.c_void_p()
+    rc = L.pml_support_tree_rule(main_newick.encode(), n, arr, int(rule), digits, C.byref(p))
     if rc:
         raise PmlError(rc, L.pml_last_error(None).decode())
     s = C.string_at(p).decode()

@@ -8,6 +8,8 @@ read like the reference's own call sites; every `run()` goes through the C ABI
   RAxMLRunner              <- .../pepr/tree/RAxMLRunner.java:64-152,162-213,320-336
   FastTreeRunner           <- .../pepr/tree/FastTreeRunner.java:38-135,142-199,235
   TreeComparison.runConsel <- .../pepr/tree/TreeComparison.java:812-885
+  buildConcatenatedTreeWithGeneWiseJackKnifeSupport
+                           <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:994-1126,1227-1275,1587-1633
 
 Behaviour kept from the reference: a failed build leaves the result `None` (FastTreeRunner.java:
 125-131 logs and continues; callers see a null tree string); the ML matrix is a RAxML model
@@ -373,3 +375,21 @@ class PhylogeneticTreeBuilder:
             self.setTreeString(f.getResult())
         else:
             raise ValueError("tree building method %r is outside the GPU path (ml, FastTree, parsimony, parsimony_bl)" % self.treeBuildingMethod)
+
+
+def buildConcatenatedTreeWithGeneWiseJackKnifeSupport(genes, reps=100, supportTreeMethod=FAST_TREE, mlMatrix="PROTGAMMAWAG",
+                                                      ctx=None, seed=1, support_rule=engine.SUPPORT_DECORATOR):
+    """PhylogenomicPipeline2.java:994-1126 as one engine call (pml_jackknife2).  genes: SequenceAlignments (or (taxa, rows)
+    pairs) of the single-copy families.  mlMatrix goes to the full tree (buildConcatenatedTree, :855-858) and, when the
+    support trees are ML trees too, to every gene-subset tree (GeneSubsetTreeRunnable.setMatrix, :1247, :1619-1620);
+    FastTree support trees (the default method, :335-338) stay WAG with FastTree_WAG's frequencies.  The supports are what
+    TreeSupportDecorator.addSupportValues counts on the returned support trees unless another rule is asked for.
+    -> the dict of Context.jackknife2: "newick" carries the supports, "support_trees" the replicate trees."""
+    if supportTreeMethod not in (ML, FAST_TREE):
+        raise ValueError("support tree method %r is outside the GPU path (ml, FastTree)" % supportTreeMethod)
+    full = _model_from_matrix(mlMatrix, ctx)                        # an unbuilt model name is refused before any device work
+    support_pi = full["pi_mode"] if supportTreeMethod == ML else engine.PI_WAG_FULL
+    ctx = ctx or default_context()
+    pairs = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
+    return ctx.jackknife2(pairs, reps=reps, seed=seed, spr_radius_full=5, pi_mode=full["pi_mode"], ncat=full["ncat"],
+                          support_pi_mode=support_pi, support_rule=support_rule)

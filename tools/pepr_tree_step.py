@@ -7,7 +7,14 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
     <run>.nwk   full ML tree of the concatenation with integer jackknife supports as node labels
     <run>.sup   the support trees, one Newick per line
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
+                         [--matrix NAME] [--support-matrix NAME] [--support-rule N]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
+--matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
+                  PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
+--support-matrix  the same for the support trees (default: the full tree's; FastTree supports are PROTGAMMAWAG)
+--support-rule    0 = only replicates over the full taxon set count, 1 = TreeSupportDecorator.addSupportValues on the support
+                  trees as written to <run>.sup, 2 = main split restricted to the replicate's taxa (include/peprml.h)
+Without these three the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
 """
 import glob
 import os
@@ -36,7 +43,7 @@ def main(argv):
     i = 0
     while i < len(argv):                       # CommandLineProperties style: -flag value
         if argv[i].startswith("-"):
-            key = argv[i][1:]; vals = []
+            key = argv[i].lstrip("-").replace("-", "_"); vals = []
             i += 1
             while i < len(argv) and not argv[i].startswith("-"):
                 vals.append(argv[i]); i += 1
@@ -51,7 +58,14 @@ def main(argv):
     reps = int(args.get("support_reps", 100))
     ctx = engine.Context(int(args.get("device", 0)))
     t0 = time.time()
-    r = ctx.jackknife(genes, reps=reps, seed=int(args.get("seed", 1)), spr_radius_full=5)
+    if {"matrix", "support_matrix", "support_rule"} & set(args):
+        from pepr_amd import tree_builder
+        full = tree_builder._model_from_matrix(args.get("matrix"), ctx)
+        sup = tree_builder._model_from_matrix(args["support_matrix"], ctx) if "support_matrix" in args else full
+        r = ctx.jackknife2(genes, reps=reps, seed=int(args.get("seed", 1)), spr_radius_full=5, pi_mode=full["pi_mode"], ncat=full["ncat"],
+                           support_pi_mode=sup["pi_mode"], support_rule=int(args.get("support_rule", 0)))
+    else:
+        r = ctx.jackknife(genes, reps=reps, seed=int(args.get("seed", 1)), spr_radius_full=5)
     dt = time.time() - t0
     run = args["run_name"]
     open(run + ".nwk", "w").write(r["newick"] + "\n")
