@@ -29,7 +29,6 @@ struct Ctx {
     int device = 0;
     bool profile = false;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;      // second lane of a chained smoothing pass (half the genes each, overlapped)
     std::mutex mu;
     std::string last_error;
     // one eigen-system per SHARED model code used on this context so far: the model and its 2*PFRAG eigen-basis fragments
@@ -63,7 +62,6 @@ struct Ctx {
     void destroy();
     int ensure_model(int pi_mode);
     hipEvent_t get_event();
-    hipStream_t tic_stream = nullptr;    // stream the next tic/toc pair is recorded on (null = stream)
     void tic(int kind, double bytes, double flops = 0);   // record start (profile mode); bytes / flops = SURVEY 8d per-operation figures
     void toc();                          // record stop
     // tic + toc for ONE launch that records its own start and end (launch_* start / stop): the pair of events to hand to it
@@ -105,6 +103,8 @@ struct Gene {
 };
 
 void det_record(int batch, const Gene &G, char kind, int a, int b, double x, double y, double z);   // PML_DET_LOG diagnostic (engine.cpp)
+double now_ms();                      // host wall clock (launch.cpp)
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct pml_alignment_view { int ntax, nsites; const char *const *names; const char *const *rows; };
 
@@ -130,6 +130,14 @@ struct PendingOp { int gene, out_kind, out_id, level; Side child[2]; double t[2]
                    int part = 0; /* run(): operations and tails of one gene with different parts are independent of each other and become separate runs
                                     of the launch (their workgroups run side by side): NNI rounds deal the edges of a gene over parts */ };
 
+// One set of launches (k_pmat, k_oplist, k_reduce, then k_newton or its SEQ form) as run() lays it out in a staging block.
+// A deferred step of a chained pass and a recorded scoring plan are each one of these; Batch::issue() launches it.
+struct LaunchSet {
+    size_t o_req = 0, o_ops = 0, o_runs = 0, o_red = 0, o_newt = 0, o_tick = 0, bytes = 0;   // offsets of the six arrays (multiples of 256), size of the block
+    size_t nreq = 0, nruns = 0, neval = 0; int nt_reg = 0, nt_stream = 0;   // matrix requests, k_oplist runs, reductions, k_newton tickets (register / streaming form)
+    bool seq = false, fused = false;                // Newton through the no-exchange SEQ form; k_oplist has fused Newton tails
+    bool any_pitch = false, any_chain = false; int max_mpad = 0; double algo_bytes = 0, algo_flops = 0, newton_bytes = 0;    // SURVEY 8d accounting
+};
 struct Batch {
     Ctx *ctx = nullptr;
     int pi_mode = 0, ncat = 4, det_id = 0;
@@ -164,16 +172,12 @@ struct Batch {
     void *h_stage = nullptr; size_t h_cap = 0;
     void *d_stage = nullptr; size_t d_cap = 0;
     double *d_frags = nullptr; size_t frag_cap = 0;      // in fragment sets
-    double *d_frags2 = nullptr; size_t frag_cap2 = 0;    // lane 1
-    double *d_nsync2 = nullptr; size_t nsync_cap2 = 0;
-    int lane = 0;                                        // which stream / buffers the next run() uses (chained passes)
-    hipEvent_t ev_stagger = nullptr; bool record_stagger = false;   // lane 1 starts one k_oplist behind lane 0
     double *d_scalars = nullptr; double *h_scalars = nullptr;   // 8 doubles per gene and tail slot: device buffer + pinned host mirror
     size_t scalars_doubles = 0, results_used = 0;
     double *h_plan_lnl = nullptr, *d_plan_lnl = nullptr;         // replayed scoring plans: one lnL per gene in mapped pinned memory (host pointer, device address)
     int fetch_results(bool pooled);                              // enqueue the device -> host copies of the result buffers
     double *d_nsync = nullptr; size_t nsync_cap = 0;             // Newton inter-workgroup sync blocks
-    NewtonCtl *d_nctl = nullptr;                                  // [2]: k_newton control block per lane (tickets, abort word)
+    NewtonCtl *d_nctl = nullptr;                                  // k_newton's control block (tickets, abort word)
     // k_newton's exchange gave up (a co-tenant kept slices of a request apart for longer than the wall-clock bound): the
     // affected work is re-issued through the no-exchange SEQ form, and the next `safe_left` Newton launch sets use it from the
     // start (doubling hold-off, so a GPU that stays shared costs one time-out per hold-off period, not one per launch)
@@ -188,9 +192,8 @@ struct Batch {
     struct ReqSrc { int gene, v, q, fold; };      // branch (v, slot q) whose length a P request uses
     struct Plan {
         bool valid = false; unsigned epoch = 0;
-        void *h = nullptr, *d = nullptr; size_t bytes = 0;
-        size_t o_req = 0, o_ops = 0, o_runs = 0, o_red = 0, nreq = 0, nruns = 0, neval = 0;
-        int max_mpad = 0; double algo_bytes = 0, algo_flops = 0; bool any_pitch = false, any_chain = false;
+        void *h = nullptr, *d = nullptr; size_t cap = 0;     // pinned host and device copy of the recorded staging block
+        LaunchSet set;
         bool stored = false;                       // recorded with every CLV written (the traversal a search runs) instead of OPF_NO_STORE
         std::vector<ReqSrc> src; std::vector<std::pair<int, int>> outs;
         std::vector<unsigned> rates_seen;          // per gene: rates_epoch the descriptors carry
@@ -206,21 +209,24 @@ struct Batch {
     bool score_only_batch = false;
     int replay_plan(double *lnl);
     bool record_plan = false, record_stored = false;
-    std::vector<ReqSrc> last_src;
-    std::vector<size_t> req_off; std::vector<uint32_t> req_stamp; std::vector<const double *> req_ptr; uint32_t req_launch = 0;   // run(): keyed request table
-    std::vector<std::vector<int>> run_tails_of; std::vector<int> run_nparts; std::vector<size_t> run_koff;
+    // run()'s scratch, kept between launches: the device waits while descriptors are built, so a launch allocates nothing
+    struct LaunchScratch {
+        std::vector<size_t> req_off; std::vector<uint32_t> req_stamp; std::vector<const double *> req_ptr; uint32_t req_launch = 0;   // keyed request table
+        std::vector<std::vector<std::pair<uint64_t, const double *>>> val_bucket; std::vector<uint32_t> val_stamp;   // requests shared by value
+        std::vector<std::vector<int>> run_tails_of; std::vector<int> run_nparts; std::vector<size_t> run_koff;       // tails, parts and first run key per gene
+        std::vector<ReqSrc> last_src; std::vector<char> fused_req; std::vector<int> tail_req;   // [request] its branch; [Newton request] fused; [tail] its Newton request or -1
+    } scratch;
     std::vector<std::vector<std::pair<int, int>>> pass_order; std::vector<std::vector<uint8_t>> pass_next;      // smooth_pass scratch
-    std::vector<std::vector<std::pair<uint64_t, const double *>>> val_bucket; std::vector<uint32_t> val_stamp;   // run(): requests shared by value
     // chained mode: run() enqueues its copy + kernels and returns WITHOUT synchronising; descriptors are bump-
     // allocated in the staging buffer; branch lengths optimised earlier in the chain are read from Gene::d_len
     bool chain = false; size_t chain_off = 0;
     double *d_lenpool = nullptr;
     double *d_chain = nullptr, *h_chain = nullptr; size_t chain_cap = 0;     // 4 doubles per chained Newton result
     // a step of a chained pass whose upload + launches are issued later, grouped with its neighbours (flush_deferred)
-    struct Deferred { size_t base, bytes, o_req, o_ops, o_runs, o_red, o_newt, o_tick, nreq, nruns, neval, nnewton; int nt_reg, nt_stream; bool seq, fused;
-                      int max_mpad, newton_maxm, lane; bool any_pitch, any_chain, stagger; double algo_bytes, newton_bytes, algo_flops; };
-    std::vector<Deferred> deferred; size_t flush_quota = 1; bool lanes_active = false;
+    struct Deferred { LaunchSet set; size_t base; /* of its block in the staging ring */ }; std::vector<Deferred> deferred; size_t flush_quota = 1;
     int flush_deferred();
+    // the launches of one set from its block at ds (device memory); self_timed: as a replayed plan, else as a flushed step
+    void issue(const LaunchSet &L, const char *ds, bool self_timed);
     int chain_begin(size_t nresults);
     int ensure_results(size_t nresults);   // d_chain (device) / h_chain (pinned mirror): 4 doubles per pooled result
     // pooled sumtables for launches that carry more Newton requests per gene than MAXTAIL (all edges of an NNI round)

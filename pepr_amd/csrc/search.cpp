@@ -1,4 +1,3 @@
-#include <chrono>
 // search.cpp -- topology search driver (NNI hill climbing) on top of the batch engine.
 //
 // Replaces the tree search inside the external programs PEPR spawns (FastTree's ML-NNI rounds,
@@ -26,7 +25,6 @@
          if (e_ != hipSuccess) return ctx->fail(-4, std::string("HIP: ") + hipGetErrorString(e_)); } while (0)
 
 namespace pml {
-static double hp_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 namespace {
 constexpr double NNI_MIN_GAIN = 0.01;
@@ -161,7 +159,7 @@ int Batch::nni_round(const std::vector<char> &active, std::vector<double> &lnl, 
     const int n = (int)genes.size();
     ++topo_epoch;
     applied.assign(n, 0);
-    double hp_t = hp_now();
+    double hp_t = now_ms();
     // per-gene edge lists in oracle order
     std::vector<std::vector<std::pair<int, int>>> edges(n);
     size_t maxsteps = 0;
@@ -255,9 +253,9 @@ int Batch::nni_round(const std::vector<char> &active, std::vector<double> &lnl, 
                 }
             }
         }
-        host_phase_ms[HP_NNI_BUILD] += hp_now() - hp_t; hp_t = hp_now();
+        host_phase_ms[HP_NNI_BUILD] += now_ms() - hp_t; hp_t = now_ms();
         if (int rc = run(ops, tails)) return rc;
-        host_phase_ms[HP_NNI_RUN] += hp_now() - hp_t; hp_t = hp_now();
+        host_phase_ms[HP_NNI_RUN] += now_ms() - hp_t; hp_t = now_ms();
         for (int g = 0; g < n; ++g) {
             if (!active[g] || e0 >= edges[g].size()) continue;
             size_t k = rbase[g];
@@ -311,7 +309,7 @@ int Batch::nni_round(const std::vector<char> &active, std::vector<double> &lnl, 
         }
         invalidate_all(g); stageA[g] = 1;
     }
-    host_phase_ms[HP_NNI_SELECT] += hp_now() - hp_t;
+    host_phase_ms[HP_NNI_SELECT] += now_ms() - hp_t;
     std::vector<double> l1(n, 0.0);
     bool any = false; for (char a : stageA) any |= a;
     if (!any) return 0;
