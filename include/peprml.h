@@ -100,7 +100,9 @@ typedef struct {
 typedef struct {
     int optimize_alpha;      /* 1: Brent on alpha */
     int nni;                 /* 1: NNI hill climbing */
-    int spr_radius;          /* >0: SPR rounds with this rearrangement radius */
+    int spr_radius;          /* >0: SPR rounds with this rearrangement radius.  pml_search, pml_search_batch, pml_batch_search,
+                              * pml_bootstrap and pml_jackknife* search at most radius 6: a larger value is cut to 6 without
+                              * an error (kept for the bits of existing callers); pml_search2 honours radii up to 25 */
     double epsilon;          /* stop when a round gains less than this many lnL units */
     unsigned seed;           /* 0: NJ start tree (deterministic); != 0: randomised stepwise-addition parsimony start with
                               * this seed, as `raxmlHPC -f d -p seed` starts (genes that come with a start tree keep it) */
@@ -151,6 +153,80 @@ int pml_optimize_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const cha
 int pml_search_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char *const *start_newicks,
                      const pml_model *model, const pml_search_opts *opts, pml_result *out);
 void pml_result_free(pml_result *r);
+
+/* RAxML's search schedule (`raxmlHPC -f d`, RAxMLRunner.java:115-147): radius determination on the start tree, fast lazy SPR
+ * cycles at that radius, final optimisation.  These are this project's definitions, written from RAxML's published algorithm
+ * (Stamatakis 2006, "RAxML-VI-HPC"); RAxML's source is not part of the reference, so parity with RAxML's own trees is NOT
+ * pinned, as everywhere else.
+ *   start     as pml_search: constraints check, coarse optimisation (epsilon 0.1) -> tree T0, lnL L0 = trace lnl_start
+ *   radius    FIXED: base.spr_radius, honoured up to PML_SPR_RADIUS_MAX (no clamp at 6; larger = PML_EINVAL).
+ *             AUTO: for r = step, 2 step, ... <= radius_max: from a copy of T0 one lazy SPR round at radius r, then the coarse
+ *             optimisation, L_r recorded; stop after the first r whose L_r does not exceed the best so far (L0 counts); the
+ *             radius is the first r that reached the maximum (radius_step if none beat L0) and the search goes on from that
+ *             trial's tree (from T0 if none).  In a batch every gene determines its own radius and stops on its own.
+ *   fast      pml_search's loop with the gene's radius: NNI rounds if base.nni, lazy SPR rounds, coarse optimisation, until
+ *             a pass applies no move.  base.nni = 0 is honoured: no NNI round runs (pml_search runs them in front of its
+ *             SPR rounds whatever nni says once spr_radius > 0, so the two calls differ for nni = 0 with a radius).
+ *   thorough  (thorough = 1, after the fast phase) distance windows [1, step], [step + 1, 2 step] ...: in a cycle every prune
+ *             scores the candidates whose distance lies in the window lazily; the thorough_top best get the thorough
+ *             insertion -- Gauss-Seidel Newton over the pendant branch and the two halves of the split edge at the search's
+ *             Newton tolerance (1e-6), until a sweep moves no length by more than that, 8 sweeps at most, then an evaluation;
+ *             the best thorough score is applied if it beats the current lnL by 0.01 and then goes through the lazy move's
+ *             apply phases (four branch Newtons, kept only if the tree really improved) from the three lengths found.  A
+ *             cycle without an accepted move shifts the gene's window by step, one with a move resets it to [1, step]; the
+ *             phase ends when the window's upper edge would pass thorough_radius_max.
+ *   end       optimisation to base.epsilon (0 = 1e-3), rates of PML_PI_GTR re-estimated, as pml_search
+ * Constraints apply at every radius.  A gene's result and trace are a function of the gene and the options alone, bit for bit,
+ * whatever shares its batch.  With radius_mode FIXED, base.spr_radius <= 6, base.nni = 1 and thorough 0 the call returns
+ * pml_search's bits.
+ * Radii above 22 need more scratch CLVs than other batches carry: a batch created by these calls gets them (min(radius,
+ * ntax) + 2 per gene), and they count in its HBM bound.  RAxML's lnL cut-off during the descent is not built: every
+ * candidate of a prune is scored in one launch. */
+#define PML_SPR_RADIUS_MAX 25
+enum { PML_RADIUS_FIXED = 0, PML_RADIUS_AUTO = 1 };
+typedef struct {
+    pml_search_opts base;     /* optimize_alpha, nni, epsilon, seed, constraints: pml_search's meaning */
+    int radius_mode;          /* FIXED: base.spr_radius (0 .. PML_SPR_RADIUS_MAX); AUTO: determined on the start tree, base.spr_radius is not used */
+    int radius_step;          /* AUTO and the thorough windows; 0 = 5 */
+    int radius_max;           /* AUTO; 0 = 25; step <= radius_max <= PML_SPR_RADIUS_MAX */
+    int thorough;             /* 1: thorough phase after the fast phase */
+    int thorough_top;         /* candidates of a prune that get the thorough insertion, best lazy scores first; 0 = all */
+    int thorough_radius_max;  /* last window's upper edge; 0 = 20; <= PML_SPR_RADIUS_MAX */
+} pml_search_opts2;
+typedef struct {              /* one accepted step */
+    int phase;                /* 0 = an NNI round (one entry per round that applied moves), 1 = lazy SPR move, 2 = thorough SPR move */
+    int rmin, rmax;           /* the window the move was found in (phase 0: 0, 0) */
+    int distance;             /* SPR: edges from the joined edge at the pruning point to the regraft edge, that edge included */
+    double lnl_before, lnl_after;
+    char *newick_after;       /* the tree after the step and its branch Newton, 12 digits */
+} pml_search_step;
+typedef struct {
+    int radius_chosen, ntrials; int *trial_radius; double *trial_lnl;   /* AUTO; FIXED: the given radius, ntrials 0 */
+    double lnl_start;         /* after the first optimisation of the start tree */
+    int nsteps; pml_search_step *steps;
+} pml_search_trace;
+int pml_search2(pml_ctx *ctx, const pml_alignment *aln, const char *start_newick /* NULL = NJ / parsimony */, const pml_model *model,
+                const pml_search_opts2 *opts, pml_result *out, pml_search_trace *trace /* NULL ok */);
+int pml_search2_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char *const *start_newicks, const pml_model *model,
+                      const pml_search_opts2 *opts, pml_result *out, pml_search_trace *traces /* n or NULL */);
+void pml_search_trace_free(pml_search_trace *t);
+/* host-only test door of the SPR candidate enumeration (the function the search itself calls): the prune cuts off the subtree
+ * whose leaves are `pruned_leaves` (names joined by '\n'; a clade or a single leaf of the tree, else PML_ENOTFOUND); returned
+ * are the regraft edges the engine would score for the window [rmin, rmax], in its order: distance_out[i] and, in *edges_out,
+ * the leaf names on the far side of edge i joined by '\n', edges separated by an empty line.  An optional constraint matrix
+ * (pml_search_opts' fields) removes the forbidden subtrees.  Release both arrays with pml_free. */
+int pml_debug_spr_enumerate(const char *newick, const char *pruned_leaves, int rmin, int rmax, int nconstraints, int constraint_ntax,
+                            const char *const *constraint_names, const char *const *constraint_rows, int *ncand_out,
+                            int **distance_out, char **edges_out);
+/* test door of the lazy SPR score (one gene, on the device): the same prune and window on the tree as given (lengths and
+ * model->alpha as given, nothing optimised); lazy_out[i] = the score the search ranks candidate i by: the lnL of the tree with
+ * the subtree regrafted into edge i, the joined branch tx + ty, the split edge halved, the pendant branch kept.
+ * thorough_top != 0 (< 0 = all): the candidates with the best lazy scores also get the thorough insertion of pml_search2:
+ * thorough_out[4 i ..] = its score, the pendant length, the near (towards the pruning point) and the far half of the split
+ * edge it settled on -- the score is the lnL of the lazy tree with these three lengths; NaN for the other candidates. */
+int pml_debug_spr_scores(pml_ctx *ctx, const pml_alignment *aln, const char *newick, const pml_model *model, const char *pruned_leaves,
+                         int rmin, int rmax, int thorough_top, int *ncand_out, int **distance_out, char **edges_out, double **lazy_out,
+                         double **thorough_out /* NULL ok when thorough_top == 0 */);
 
 /* Models beyond WAG.  A rate matrix is 190 exchangeabilities -- the lower triangle by rows, (1,0), (2,0), (2,1), (3,0) ... in
  * the state order ARNDCQEGHILKMFPSTWYV -- and 20 frequencies: the layout of PAML's .dat files.

@@ -23,6 +23,7 @@ SYMBOLS = [
     "pml_au_fit", "pml_rell_tests", "pml_tree_tests", "pml_tree_test_result_free", "pml_debug_rell",
     "pml_rell_tests_weighted", "pml_tree_tests_weighted", "pml_tree_test_weighted_free", "pml_debug_rell_weighted", "pml_catpv_table",
     "pml_jackknife2", "pml_support_tree_rule", "pml_debug_replicate_freqs",
+    "pml_search2", "pml_search2_batch", "pml_search_trace_free", "pml_debug_spr_enumerate", "pml_debug_spr_scores",
 ]
 
 
@@ -44,6 +45,22 @@ class SearchOpts(C.Structure):
                 ("epsilon", C.c_double), ("seed", C.c_uint),
                 ("nconstraints", C.c_int), ("constraint_ntax", C.c_int),
                 ("constraint_names", C.POINTER(C.c_char_p)), ("constraint_rows", C.POINTER(C.c_char_p))]
+
+
+class SearchOpts2(C.Structure):
+    _fields_ = [("base", SearchOpts), ("radius_mode", C.c_int), ("radius_step", C.c_int), ("radius_max", C.c_int),
+                ("thorough", C.c_int), ("thorough_top", C.c_int), ("thorough_radius_max", C.c_int)]
+
+
+class SearchStep(C.Structure):
+    _fields_ = [("phase", C.c_int), ("rmin", C.c_int), ("rmax", C.c_int), ("distance", C.c_int),
+                ("lnl_before", C.c_double), ("lnl_after", C.c_double), ("newick_after", C.c_void_p)]
+
+
+class SearchTrace(C.Structure):
+    _fields_ = [("radius_chosen", C.c_int), ("ntrials", C.c_int), ("trial_radius", C.POINTER(C.c_int)),
+                ("trial_lnl", C.POINTER(C.c_double)), ("lnl_start", C.c_double), ("nsteps", C.c_int),
+                ("steps", C.POINTER(SearchStep))]
 
 
 class JackknifeOpts(C.Structure):
@@ -175,5 +192,13 @@ def load():
     L.pml_debug_rell_weighted.argtypes = [vp, C.c_longlong, C.c_int, dp, C.c_int, lp, C.c_longlong, C.c_ulonglong, C.c_int, dp, lp, lp, lp, ip, dp,
                                           dp, dp, lp, lp]
     L.pml_catpv_table.argtypes = [trp, twp, C.POINTER(vp)]
+    s2p, stp = C.POINTER(SearchOpts2), C.POINTER(SearchTrace)
+    L.pml_search2.argtypes = [vp, ap, C.c_char_p, mp, s2p, rp, stp]
+    L.pml_search2_batch.argtypes = [vp, C.c_int, ap, cpp, mp, s2p, rp, stp]
+    L.pml_search_trace_free.argtypes = [stp]
+    L.pml_search_trace_free.restype = None
+    L.pml_debug_spr_enumerate.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, cpp, cpp, ip, C.POINTER(vp), C.POINTER(vp)]
+    L.pml_debug_spr_scores.argtypes = [vp, ap, C.c_char_p, mp, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(vp), C.POINTER(vp),
+                                       C.POINTER(vp), C.POINTER(vp)]
     _lib = L
     return L

@@ -205,17 +205,22 @@ int pml_batch_newick(pml_batch *b, int g, int digits, char **out) {
 
 // ---- one-shot wrappers --------------------------------------------------------------------
 enum { OP_SCORE, OP_OPTIMIZE, OP_SEARCH };
+// pml_search2 travels the one-shot path as OP_SEARCH with this attached: the schedule and where each gene's trace goes
+struct Search2Job { Search2Opts o; pml_search_trace *const *traces; /* per gene of the (sub-)batch, or null */
+                    int scratch_radius() const { return std::max(o.radius_auto ? o.radius_max : o.radius, o.thorough ? o.thorough_radius_max : 0); } };
+static int fill_trace(const SearchTrace &t, pml_search_trace *out);
 
 // upper bound of the HBM a gene needs in a batch (patterns <= columns)
-static size_t gene_bytes_bound(const pml_alignment &a, bool score_only) {
+static size_t gene_bytes_bound(const pml_alignment &a, bool score_only, int spr_radius = 0 /* search2 batches: Batch::spr_scratch_radius */) {
     const size_t mp = ((size_t)std::max(a.nsites, 1) + 31) / 32 * 32, nt = (size_t)std::max(a.ntax, 3);
-    const size_t slots = (score_only ? nt - 2 : 3 * (nt - 2)) + NSCRATCH + MAXTAIL;
+    const size_t slots = (score_only ? nt - 2 : 3 * (nt - 2)) + std::max<size_t>(NSCRATCH, std::min<size_t>((size_t)spr_radius, nt) + 2) + MAXTAIL;
     return slots * CLV_ROWS * ((mp + 127) / 128 * 128) * 8 + slots * mp * 4 + nt * mp + 64 * mp + (1 << 16);
 }
 
 // one device batch on context `c` (the caller's own or one of its workers): start trees, the requested operation, results
 static int oneshot_on(Ctx &c, int op, int n, const pml_alignment *alns, const char *const *newicks,
-                      const pml_model *model, const pml_search_opts *opts, int flags, pml_result *const *out, int share) {
+                      const pml_model *model, const pml_search_opts *opts, int flags, pml_result *const *out, int share,
+                      const Search2Job *s2 = nullptr) {
     pml_fpguard fpg;
     // RAxML starts `-f d` from a randomised stepwise-addition parsimony tree (-p seed): opts->seed != 0 asks for
     // that start for every gene without a given start tree (seed 0 = the deterministic NJ start)
@@ -238,6 +243,7 @@ static int oneshot_on(Ctx &c, int op, int n, const pml_alignment *alns, const ch
     Batch b;
     struct Drop { Batch &b; ~Drop() { b.destroy(); } } drop{b};
     b.share = share;
+    if (s2) b.spr_scratch_radius = s2->scratch_radius();
     int rc;
     try {
         rc = b.create(&c, n, reinterpret_cast<const pml_alignment_view *>(alns), newicks, model ? model->pi_mode : PML_PI_RAXML_3DP,
@@ -249,8 +255,11 @@ static int oneshot_on(Ctx &c, int op, int n, const pml_alignment *alns, const ch
             rc = b.optimize(opts ? opts->optimize_alpha != 0 : true, (opts && opts->epsilon > 0) ? opts->epsilon : 1e-4, lnl.data());
         else {
             rc = opts ? b.set_constraints(opts->nconstraints, opts->constraint_ntax, opts->constraint_names, opts->constraint_rows) : 0;
-            if (!rc) rc = b.search(opts ? opts->nni != 0 : true, opts ? opts->spr_radius : 0, opts ? opts->optimize_alpha != 0 : true,
-                                   (opts && opts->epsilon > 0) ? opts->epsilon : 1e-3, lnl.data());
+            std::vector<SearchTrace> tr;
+            if (!rc && s2) rc = b.search2(s2->o, lnl.data(), s2->traces ? &tr : nullptr);
+            else if (!rc) rc = b.search(opts ? opts->nni != 0 : true, opts ? opts->spr_radius : 0, opts ? opts->optimize_alpha != 0 : true,
+                                        (opts && opts->epsilon > 0) ? opts->epsilon : 1e-3, lnl.data());
+            for (int i = 0; i < n && !rc && s2 && s2->traces; ++i) if (fill_trace(tr[i], s2->traces[i])) rc = c.fail(PML_ENOMEM, "host allocation failed");
         }
         for (int i = 0; i < n && !rc; ++i) {
             const Gene &G = b.genes[i];
@@ -301,12 +310,12 @@ static int search_groups(int n, const pml_alignment *alns) {
 }
 
 static int oneshot_chunk(pml_ctx *ctx, int op, int n, const pml_alignment *alns, const char *const *newicks,
-                         const pml_model *model, const pml_search_opts *opts, int flags, pml_result *out) {
+                         const pml_model *model, const pml_search_opts *opts, int flags, pml_result *out, const Search2Job *s2 = nullptr) {
     const int G = (op == OP_SEARCH) ? search_groups(n, alns) : 1;
     if (G <= 1) {
         std::vector<pml_result *> outs(n);
         for (int i = 0; i < n; ++i) outs[i] = out + i;
-        return oneshot_on(ctx->c, op, n, alns, newicks, model, opts, flags, outs.data(), 1);
+        return oneshot_on(ctx->c, op, n, alns, newicks, model, opts, flags, outs.data(), 1, s2);
     }
     // genes are dealt round-robin (the callers pass genes of similar size next to each other), group k on worker context k
     for (int k = 0; k < G; ++k) if (!worker_ctx(ctx, k)) return PML_EDEVICE;
@@ -315,8 +324,10 @@ static int oneshot_chunk(pml_ctx *ctx, int op, int n, const pml_alignment *alns,
     std::vector<std::thread> th;
     for (int k = 0; k < G; ++k) th.emplace_back([&, k]() {
         std::vector<pml_alignment> a; std::vector<const char *> nw; std::vector<pml_result *> outs;
-        for (int i = k; i < n; i += G) { a.push_back(alns[i]); nw.push_back(newicks ? newicks[i] : nullptr); outs.push_back(out + i); }
-        try { rcs[k] = oneshot_on(*ctx->workers[k], op, (int)a.size(), a.data(), newicks ? nw.data() : nullptr, model, opts, flags, outs.data(), G); }
+        std::vector<pml_search_trace *> trs; Search2Job job;
+        for (int i = k; i < n; i += G) { a.push_back(alns[i]); nw.push_back(newicks ? newicks[i] : nullptr); outs.push_back(out + i); if (s2 && s2->traces) trs.push_back(s2->traces[i]); }
+        if (s2) { job = *s2; job.traces = s2->traces ? trs.data() : nullptr; }
+        try { rcs[k] = oneshot_on(*ctx->workers[k], op, (int)a.size(), a.data(), newicks ? nw.data() : nullptr, model, opts, flags, outs.data(), G, s2 ? &job : nullptr); }
         catch (const std::exception &e) { rcs[k] = ctx->workers[k]->fail(PML_EINVAL, e.what()); }
     });
     for (auto &t : th) t.join();
@@ -337,7 +348,7 @@ static int oneshot_chunk(pml_ctx *ctx, int op, int n, const pml_alignment *alns,
 // one-shot batched call; gene lists that do not fit in free HBM at once are processed in
 // consecutive sub-batches (e.g. BASELINE config C5: 250 genes x 500 taxa x 2000 sites per GPU)
 static int oneshot(pml_ctx *ctx, int op, int n, const pml_alignment *alns, const char *const *newicks,
-                   const pml_model *model, const pml_search_opts *opts, int flags, pml_result *out) {
+                   const pml_model *model, const pml_search_opts *opts, int flags, pml_result *out, const Search2Job *s2 = nullptr) {
     if (!ctx || !alns || !out || n <= 0) return PML_EINVAL;
     pml_fpguard fpg;                               // also when this thread is the leader running other callers' requests
     for (int i = 0; i < n; ++i) std::memset(&out[i], 0, sizeof(pml_result));
@@ -359,11 +370,13 @@ static int oneshot(pml_ctx *ctx, int op, int n, const pml_alignment *alns, const
     while (begin < n && !rc) {
         size_t used = 0; int end = begin;
         while (end < n) {
-            const size_t need = gene_bytes_bound(alns[end], op == OP_SCORE);
+            const size_t need = gene_bytes_bound(alns[end], op == OP_SCORE, s2 ? s2->scratch_radius() : 0);
             if (end > begin && used + need > budget) break;
             used += need; ++end;
         }
-        rc = oneshot_chunk(ctx, op, end - begin, alns + begin, newicks ? newicks + begin : nullptr, model, opts, flags, out + begin);
+        Search2Job job;
+        if (s2) { job = *s2; if (s2->traces) job.traces = s2->traces + begin; }
+        rc = oneshot_chunk(ctx, op, end - begin, alns + begin, newicks ? newicks + begin : nullptr, model, opts, flags, out + begin, s2 ? &job : nullptr);
         begin = end;
     }
     for (int i = 0; i < n; ++i) out[i].status = rc;
@@ -471,6 +484,168 @@ int pml_optimize_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const cha
 int pml_search_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char *const *starts,
                      const pml_model *model, const pml_search_opts *opts, pml_result *out) {
     return oneshot(ctx, OP_SEARCH, n, alns, starts, model, opts, 0, out);
+}
+
+// ---- RAxML's search schedule ----------------------------------------------------------------
+static int fill_trace(const SearchTrace &t, pml_search_trace *out) {
+    std::memset(out, 0, sizeof *out);
+    out->radius_chosen = t.radius_chosen; out->lnl_start = t.lnl_start;
+    out->ntrials = (int)t.trial_radius.size(); out->nsteps = (int)t.steps.size();
+    out->trial_radius = (int *)std::malloc(sizeof(int) * std::max(out->ntrials, 1));
+    out->trial_lnl = (double *)std::malloc(sizeof(double) * std::max(out->ntrials, 1));
+    out->steps = (pml_search_step *)std::calloc((size_t)std::max(out->nsteps, 1), sizeof(pml_search_step));
+    if (!out->trial_radius || !out->trial_lnl || !out->steps) { pml_search_trace_free(out); return PML_ENOMEM; }
+    for (int i = 0; i < out->ntrials; ++i) { out->trial_radius[i] = t.trial_radius[i]; out->trial_lnl[i] = t.trial_lnl[i]; }
+    for (int i = 0; i < out->nsteps; ++i) {
+        const SearchStep &s = t.steps[i];
+        out->steps[i] = pml_search_step{s.phase, s.rmin, s.rmax, s.distance, s.lnl_before, s.lnl_after, dup_string(s.newick_after)};
+        if (!out->steps[i].newick_after) { pml_search_trace_free(out); return PML_ENOMEM; }
+    }
+    return PML_OK;
+}
+void pml_search_trace_free(pml_search_trace *t) {
+    if (!t) return;
+    if (t->steps) for (int i = 0; i < t->nsteps; ++i) std::free(t->steps[i].newick_after);
+    std::free(t->steps); std::free(t->trial_radius); std::free(t->trial_lnl);
+    std::memset(t, 0, sizeof *t);
+}
+int pml_search2_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const char *const *starts, const pml_model *model,
+                      const pml_search_opts2 *opts, pml_result *out, pml_search_trace *traces) {
+    if (!ctx || !alns || !out || n <= 0) return PML_EINVAL;
+    if (traces) std::memset(traces, 0, sizeof(pml_search_trace) * (size_t)n);
+    if (!opts) return ctx->c.fail(PML_EINVAL, "pml_search2: options required");
+    Search2Job job;
+    job.o.nni = opts->base.nni != 0; job.o.opt_alpha = opts->base.optimize_alpha != 0;
+    job.o.eps = opts->base.epsilon > 0 ? opts->base.epsilon : 1e-3;
+    job.o.radius_auto = opts->radius_mode == PML_RADIUS_AUTO;
+    job.o.radius = opts->base.spr_radius; job.o.radius_step = opts->radius_step ? opts->radius_step : 5;
+    job.o.radius_max = opts->radius_max ? opts->radius_max : PML_SPR_RADIUS_MAX;
+    if (opts->radius_mode != PML_RADIUS_FIXED && opts->radius_mode != PML_RADIUS_AUTO) return ctx->c.fail(PML_EINVAL, "pml_search2: bad radius_mode");
+    if (opts->radius_step < 0 || opts->radius_max < 0) return ctx->c.fail(PML_EINVAL, "pml_search2: negative radius_step / radius_max");
+    if (!job.o.radius_auto && (job.o.radius < 0 || job.o.radius > PML_SPR_RADIUS_MAX)) return ctx->c.fail(PML_EINVAL, "pml_search2: spr_radius outside 0..25 (no clamp)");
+    if (job.o.radius_auto && (job.o.radius_max > PML_SPR_RADIUS_MAX || job.o.radius_step > job.o.radius_max)) return ctx->c.fail(PML_EINVAL, "pml_search2: radius_step <= radius_max <= 25 required");
+    job.o.thorough = opts->thorough != 0; job.o.thorough_top = opts->thorough_top;
+    job.o.thorough_radius_max = opts->thorough_radius_max ? opts->thorough_radius_max : 20;
+    if (opts->thorough_top < 0 || opts->thorough_radius_max < 0 || job.o.thorough_radius_max > PML_SPR_RADIUS_MAX)
+        return ctx->c.fail(PML_EINVAL, "pml_search2: thorough_top >= 0 and 0 <= thorough_radius_max <= 25 required");
+    if (job.o.radius_auto) job.o.radius = 0;
+    std::vector<pml_search_trace *> trs;
+    if (traces) for (int i = 0; i < n; ++i) trs.push_back(traces + i);
+    job.traces = traces ? trs.data() : nullptr;
+    const int rc = oneshot(ctx, OP_SEARCH, n, alns, starts, model, &opts->base, 0, out, &job);
+    if (rc && traces) for (int i = 0; i < n; ++i) pml_search_trace_free(traces + i);
+    return rc;
+}
+int pml_search2(pml_ctx *ctx, const pml_alignment *aln, const char *start, const pml_model *model, const pml_search_opts2 *opts,
+                pml_result *out, pml_search_trace *trace) {
+    if (!aln) return PML_EINVAL;
+    return pml_search2_batch(ctx, 1, aln, start ? &start : nullptr, model, opts, out, trace);
+}
+
+// the prune (p, slot) that cuts the subtree with the given leaves off, or false
+static bool find_prune(const Tree &T, const std::vector<std::string> &names, const char *pruned, int &p, int &ks, std::string &err) {
+    const int nt = T.ntax, words = (nt + 63) / 64;
+    std::vector<uint64_t> X(words, 0);
+    std::string cur; int cnt = 0;
+    for (const char *c = pruned;; ++c) {
+        if (*c == '\n' || *c == 0) {
+            if (!cur.empty()) {
+                int t = -1; for (int i = 0; i < nt; ++i) if (names[i] == cur) { t = i; break; }
+                if (t < 0) { err = "pruned leaf " + cur + " is not in the tree"; return false; }
+                X[t >> 6] |= 1ULL << (t & 63); ++cnt; cur.clear();
+            }
+            if (*c == 0) break;
+        } else cur.push_back(*c);
+    }
+    if (cnt < 1 || cnt > nt - 3) { err = "the pruned subtree must leave at least three leaves"; return false; }
+    const auto leafs = leaf_sets(T);
+    for (p = nt; p < T.nnodes(); ++p) for (ks = 0; ks < 3; ++ks) {
+        const int s = T.nbr[p][ks];
+        if (s < nt) { if (cnt == 1 && (X[s >> 6] >> (s & 63) & 1)) return true; }
+        else if (leafs[(s - nt) * 3 + T.slot(s, p)] == X) return true;
+    }
+    err = "the pruned leaves are not a subtree";
+    return false;
+}
+// distances and far-side leaf sets of the candidates, as the doors return them
+static int export_candidates(const Tree &T, const std::vector<std::string> &names, const std::vector<SprCandidate> &cands,
+                             int *ncand_out, int **distance_out, char **edges_out) {
+    const int nt = T.ntax;
+    const auto leafs = leaf_sets(T);
+    std::string txt;
+    int *dist = (int *)std::malloc(sizeof(int) * std::max<size_t>(cands.size(), 1));
+    if (!dist) return PML_ENOMEM;
+    for (size_t i = 0; i < cands.size(); ++i) {
+        dist[i] = cands[i].distance;
+        if (i) txt += "\n\n";
+        const int g = cands[i].g, h = cands[i].h;
+        bool first = true;
+        for (int t = 0; t < nt; ++t) {
+            const bool in = h < nt ? t == h : (leafs[(h - nt) * 3 + T.slot(h, g)][t >> 6] >> (t & 63) & 1) != 0;
+            if (!in) continue;
+            if (!first) txt += "\n";
+            txt += names[t]; first = false;
+        }
+    }
+    *edges_out = dup_string(txt);
+    if (!*edges_out) { std::free(dist); return PML_ENOMEM; }
+    *distance_out = dist; *ncand_out = (int)cands.size();
+    return PML_OK;
+}
+int pml_debug_spr_enumerate(const char *newick, const char *pruned_leaves, int rmin, int rmax, int nconstraints, int constraint_ntax,
+                            const char *const *constraint_names, const char *const *constraint_rows, int *ncand_out,
+                            int **distance_out, char **edges_out) {
+    if (!newick || !pruned_leaves || !ncand_out || !distance_out || !edges_out || rmin < 1 || rmax < rmin) return PML_EINVAL;
+    if (nconstraints > 0 && (constraint_ntax <= 0 || !constraint_names || !constraint_rows)) return PML_EINVAL;
+    try {
+        Tree T; std::vector<std::string> names; std::string err;
+        if (!Tree::parse_free(newick, names, T, err)) { g_err = err; return PML_EPARSE; }
+        if (T.ntax < 5) { g_err = "an SPR needs five leaves"; return PML_EINVAL; }
+        int p, ks;
+        if (!find_prune(T, names, pruned_leaves, p, ks, err)) { g_err = err; return PML_ENOTFOUND; }
+        std::vector<Constraint> cons;
+        if (nconstraints > 0) {
+            for (int i = 0; i < constraint_ntax; ++i) if (!constraint_names[i] || !constraint_rows[i] || (int)strnlen(constraint_rows[i], (size_t)nconstraints) < nconstraints) return PML_EINVAL;
+            cons = constraints_for(names, nconstraints, constraint_ntax, constraint_names, constraint_rows);
+        }
+        std::vector<SprCandidate> cands;
+        spr_candidates(T, cons, p, ks, rmin, rmax, cands);
+        return export_candidates(T, names, cands, ncand_out, distance_out, edges_out);
+    } catch (const std::exception &e) { g_err = e.what(); return PML_ENOMEM; }
+}
+int pml_debug_spr_scores(pml_ctx *ctx, const pml_alignment *aln, const char *newick, const pml_model *model, const char *pruned_leaves,
+                         int rmin, int rmax, int thorough_top, int *ncand_out, int **distance_out, char **edges_out, double **lazy_out,
+                         double **thorough_out) {
+    if (!ctx || !aln || !newick || !pruned_leaves || !ncand_out || !distance_out || !edges_out || !lazy_out) return PML_EINVAL;
+    if (rmin < 1 || rmax < rmin || rmax > PML_SPR_RADIUS_MAX) return ctx->c.fail(PML_EINVAL, "pml_debug_spr_scores: bad window");
+    if (thorough_top != 0 && !thorough_out) return ctx->c.fail(PML_EINVAL, "pml_debug_spr_scores: thorough_out required");
+    pml_fpguard fpg;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    pml_drop_worker_caches(ctx);
+    Batch b;
+    struct Drop { Batch &b; ~Drop() { b.destroy(); } } drop{b};
+    b.spr_scratch_radius = rmax;
+    try {
+        int rc = b.create(&ctx->c, 1, reinterpret_cast<const pml_alignment_view *>(aln), &newick, model ? model->pi_mode : PML_PI_RAXML_3DP,
+                          model ? model->ncat : 4, model ? model->alpha : 1.0, false);
+        if (rc) return rc;
+        const Gene &G = b.genes[0];
+        int p, ks; std::string err;
+        if (G.tree.ntax < 5) return ctx->c.fail(PML_EINVAL, "an SPR needs five leaves");
+        if (!find_prune(G.tree, G.aln.names, pruned_leaves, p, ks, err)) return ctx->c.fail(PML_ENOTFOUND, err);
+        std::vector<SprCandidate> cands; std::vector<double> lazy; std::vector<std::array<double, 4>> th;
+        if ((rc = b.spr_scores(p, ks, rmin, rmax, thorough_top, cands, lazy, th))) return rc;
+        double *lz = (double *)std::malloc(sizeof(double) * std::max<size_t>(lazy.size(), 1));
+        double *tz = (double *)std::malloc(sizeof(double) * 4 * std::max<size_t>(lazy.size(), 1));
+        if (!lz || !tz) { std::free(lz); std::free(tz); return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+        for (size_t i = 0; i < lazy.size(); ++i) { lz[i] = lazy[i]; for (int q = 0; q < 4; ++q) tz[4 * i + q] = th[i][q]; }
+        rc = export_candidates(G.tree, G.aln.names, cands, ncand_out, distance_out, edges_out);
+        if (rc) { std::free(lz); std::free(tz); return ctx->c.fail(rc, "host allocation failed"); }
+        *lazy_out = lz;
+        if (thorough_out) *thorough_out = tz; else std::free(tz);
+        return PML_OK;
+    } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+    catch (const std::exception &e) { return ctx->c.fail(PML_EINVAL, e.what()); }
 }
 
 // ---- models beyond WAG --------------------------------------------------------------------

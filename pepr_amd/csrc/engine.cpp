@@ -378,13 +378,15 @@ int Batch::layout(double alpha, bool score_only) {
         Gene &G = genes[g];
         const int nt = G.aln.ntax, mp = G.aln.mpad, ndir = 3 * (nt - 2);
         G.slot_cap = score_only ? (nt - 2) : ndir;
+        // a search2 batch: SPR path CLVs for every depth the gene's taxon count can reach, + insertion slot + one spare
+        G.nscratch = std::max(NSCRATCH, std::min(spr_scratch_radius, nt) + 2);
         G.slot_of.assign(ndir, -1); G.valid.assign(ndir, 0); G.pend_level.assign(ndir, -1);
         G.mark_all();
         off[g] = total;
         total += align_up((size_t)nt * mp, 256);                       // codes
         total += align_up((size_t)mp * 8, 256);                        // weight
-        total += (size_t)(G.slot_cap + NSCRATCH) * clv_doubles(mp) * 8;  // clv (+ scratch), tiled: whole 128-pattern tiles
-        total += align_up((size_t)(G.slot_cap + NSCRATCH) * mp * 4, 256);   // scalers
+        total += (size_t)(G.slot_cap + G.nscratch) * clv_doubles(mp) * 8;  // clv (+ scratch), tiled: whole 128-pattern tiles
+        total += align_up((size_t)(G.slot_cap + G.nscratch) * mp * 4, 256);   // scalers
         total += (size_t)MAXTAIL * clv_doubles(mp) * 8;                  // sumtables
         total += (size_t)MAXTAIL * align_up((size_t)mp * 4, 256);      // sumtable scalers
         total += (size_t)MAXTAIL * align_up((size_t)mp * 8, 256);      // per-pattern lnL
@@ -410,8 +412,8 @@ int Batch::layout(double alpha, bool score_only) {
         char *p = arena + off[g];
         G.d_codes = (uint8_t *)p; p += align_up((size_t)nt * mp, 256);
         G.d_weight = (double *)p; p += align_up((size_t)mp * 8, 256);
-        G.d_clv = (double *)p; p += (size_t)(G.slot_cap + NSCRATCH) * clv_doubles(mp) * 8;
-        G.d_scl = (int *)p; p += align_up((size_t)(G.slot_cap + NSCRATCH) * mp * 4, 256);
+        G.d_clv = (double *)p; p += (size_t)(G.slot_cap + G.nscratch) * clv_doubles(mp) * 8;
+        G.d_scl = (int *)p; p += align_up((size_t)(G.slot_cap + G.nscratch) * mp * 4, 256);
         for (int k = 0; k < MAXTAIL; ++k) { G.d_sumtab[k] = (double *)p; p += clv_doubles(mp) * 8; }
         for (int k = 0; k < MAXTAIL; ++k) { G.d_sumscl[k] = (int *)p; p += align_up((size_t)mp * 4, 256); }
         for (int k = 0; k < MAXTAIL; ++k) { G.d_patlnl[k] = (double *)p; p += align_up((size_t)mp * 8, 256); }

@@ -90,6 +90,7 @@ struct Gene {
     int *d_sumscl[MAXTAIL] = {};       // mpad each
     double *d_patlnl[MAXTAIL] = {};    // mpad each
     int slot_cap = 0, next_slot = 0;
+    int nscratch = 0;              // scratch CLV slots behind the slot_cap message slots (NSCRATCH; more in a search2 batch)
     std::vector<int> slot_of;      // directed-edge index (v-ntax)*3+k -> slot (-1 = none)
     std::vector<uint8_t> valid;
     std::vector<int> pend_level;   // scratch for collection (-1 = not pending)
@@ -138,6 +139,15 @@ struct LaunchSet {
     bool seq = false, fused = false;                // Newton through the no-exchange SEQ form; k_oplist has fused Newton tails
     bool any_pitch = false, any_chain = false; int max_mpad = 0; double algo_bytes = 0, algo_flops = 0, newton_bytes = 0;    // SURVEY 8d accounting
 };
+// pml_search2: one accepted step of a gene's search, and the record of the whole search (peprml.h pml_search_trace)
+struct SearchStep { int phase, rmin, rmax, distance; double lnl_before, lnl_after; std::string newick_after; };
+struct SearchTrace { int radius_chosen = 0; std::vector<int> trial_radius; std::vector<double> trial_lnl; double lnl_start = 0; std::vector<SearchStep> steps; };
+struct Search2Opts { bool nni = true, opt_alpha = true; double eps = 1e-3; bool radius_auto = false; int radius = 0, radius_step = 5, radius_max = 25;
+                     bool thorough = false; int thorough_top = 0, thorough_radius_max = 20; };
+// one thorough insertion: the subtree cut off by prune (p, ks) of gene g regrafted into the candidate's edge with the pendant
+// branch ts and the two halves tg, th of the split edge optimised (in: start values; out: what the sweeps settled on), score =
+// the lnL of that tree with nothing else touched
+struct ThoroughJob { int g, p, ks; SprCandidate cand; double ts, tg, th, score; int sweeps; };
 struct Batch {
     Ctx *ctx = nullptr;
     int pi_mode = 0, ncat = 4, det_id = 0;
@@ -164,6 +174,7 @@ struct Batch {
     int opt_rates(const std::vector<char> &active, double *lnl, double tol);
     bool rates_on = true;          // optimize() estimates the rates of GTR genes (a search holds them fixed between its first and last optimisation)
     long cnt_rate_trials = 0;
+    int spr_scratch_radius = 0;    // set before create(): the largest SPR radius the batch will search (search2 batches; 0 = NSCRATCH serves)
     int share = 1;                 // batches working on the device at the same time (groups of one search call): free HBM is divided by it
     double newton_tol = 1e-8;      // Newton stop |dt| < tol: 1e-8 fine, 1e-6 in coarse phases
     std::vector<Gene> genes;
@@ -263,6 +274,22 @@ struct Batch {
     int nni_round(const std::vector<char> &active, std::vector<double> &lnl, std::vector<int> &applied);
     int spr_round(const std::vector<char> &active, int radius, std::vector<double> &lnl, std::vector<int> &moves);
     int search(bool nni, int spr_radius, bool opt_alpha_flag, double eps, double *lnl);
+    // the lazy SPR round with a radius per gene and a distance window [rmin, radius]; radii beyond what the gene's scratch
+    // slots serve are cut to that; trace (optional, per gene): every kept move is appended as a phase-1 step
+    int spr_round_windowed(const std::vector<char> &active, const std::vector<int> &radius, int rmin, std::vector<double> &lnl,
+                           std::vector<int> &moves, std::vector<SearchTrace> *trace);
+    // RAxML's schedule (peprml.h pml_search2): radius determination, fast phase, final optimisation
+    int search2(const Search2Opts &o, double *lnl, std::vector<SearchTrace> *trace);
+    // test door: the lazy scores of the candidates of one prune of gene 0, in spr_candidates' order, and the thorough
+    // insertions of the thorough_top best of them (0 = none, < 0 = all): thorough[i] = {score, ts, tg, th} or NaNs
+    int spr_scores(int p, int ks, int rmin, int rmax, int thorough_top, std::vector<SprCandidate> &cands, std::vector<double> &lazy,
+                   std::vector<std::array<double, 4>> &thorough);
+    // Gauss-Seidel Newton over the three branches of every job (<= 8 sweeps, stop when a sweep moves no length by more than
+    // newton_tol), then its evaluation; all jobs of all genes advance in lockstep, one launch set per Newton
+    int thorough_insert(std::vector<ThoroughJob> &jobs);
+    // one cycle of the thorough phase: every prune of every active gene, candidates within the gene's window
+    int thorough_cycle(const std::vector<char> &active, const std::vector<int> &rmin, const std::vector<int> &rmax, int top,
+                       std::vector<double> &lnl, std::vector<int> &moves, std::vector<SearchTrace> *trace);
     // SH-like local supports (FastTree's default output; FastTreeRunner.java:67-70 without -nosupport): per gene one value
     // per internal edge in nni_round's edge order (u ascending, slot ascending, v > u inner), plus the (u, v) pairs
     // FastTree -gamma: per-pattern likelihoods at the 20 fixed rates (five traversals of four rates), then alpha and the

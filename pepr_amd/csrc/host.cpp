@@ -738,6 +738,54 @@ bool tree_displays(const Tree &t, const std::vector<Constraint> &cs) {
     return true;
 }
 
+void spr_candidates(const Tree &T, const std::vector<Constraint> &cons, int p, int ks, int rmin, int rmax, std::vector<SprCandidate> &out) {
+    out.clear();
+    const int nt = T.ntax, s = T.nbr[p][ks];
+    int xy[2], ci = 0;
+    for (int q = 0; q < 3; ++q) if (q != ks) xy[ci++] = T.nbr[p][q];
+    // constraints: regrafting beyond edge (gg,h) turns its split into L(h side) + L(S); if that is
+    // incompatible, neither this edge nor anything behind it is a candidate
+    std::vector<std::vector<uint64_t>> leafs; std::vector<uint64_t> LS;
+    if (!cons.empty()) {
+        leafs = leaf_sets(T);
+        LS.assign((nt + 63) / 64, 0);
+        if (s < nt) LS[s >> 6] |= 1ULL << (s & 63); else LS = leafs[(s - nt) * 3 + T.slot(s, p)];
+    }
+    auto allowed = [&](int gg, int h) {
+        if (cons.empty()) return true;
+        std::vector<uint64_t> X((nt + 63) / 64, 0);
+        if (h < nt) X[h >> 6] |= 1ULL << (h & 63); else X = leafs[(h - nt) * 3 + T.slot(h, gg)];
+        for (size_t w = 0; w < X.size(); ++w) X[w] |= LS[w];
+        return compatible_with_all(cons, X);
+    };
+    std::vector<SprStep> pending, trail;      // path CLVs no emitted candidate has built yet; those of the walk's current position
+    struct Walk {
+        const Tree &T; int nt, rmin, rmax; std::vector<SprStep> &pending, &trail; std::vector<SprCandidate> &out; decltype(allowed) &ok;
+        void children(int from, int at, int depth, int skip) {      // descend from `at` (entered from `from`; depth 0: skip = p)
+            int ch[2], c = 0;
+            for (int q = 0; q < 3; ++q) if (T.nbr[at][q] != skip) ch[c++] = T.nbr[at][q];
+            for (int i = 0; i < 2; ++i) {
+                const size_t mark = pending.size();
+                pending.push_back({depth, from, at, ch[1 - i]}); trail.push_back(pending.back());
+                explore(at, ch[i], depth + 1);
+                trail.pop_back();
+                if (pending.size() > mark) pending.resize(mark);        // nothing behind this edge was a candidate
+            }
+        }
+        void explore(int gg, int h, int depth) {
+            if (!ok(gg, h)) return;
+            if (depth >= rmin) { out.push_back({gg, h, depth, pending, trail}); pending.clear(); }
+            if (h < nt || depth >= rmax) return;
+            children(gg, h, depth, gg);
+        }
+    } walk{T, nt, rmin, rmax, pending, trail, out, allowed};
+    for (int sidei = 0; sidei < 2; ++sidei) {
+        const int a = xy[sidei], b = xy[1 - sidei];
+        if (a < nt) continue;
+        walk.children(b, a, 0, p);
+    }
+}
+
 // comparable / differing column counts of every taxon pair (integer weights: exact, so the counts of a
 // concatenation are the sums of its genes' counts -- the replicate path never touches the columns again)
 void pair_counts(const EncodedAlignment &a, std::vector<int64_t> &cmp, std::vector<int64_t> &diff) {

@@ -99,6 +99,23 @@ bool compatible_with_all(const std::vector<Constraint> &cs, const std::vector<ui
 // leaf sets of all directed messages: L[(v-ntax)*3+k] = taxa on v's side of edge (v, nbr[v][k])
 std::vector<std::vector<uint64_t>> leaf_sets(const Tree &t);
 bool tree_displays(const Tree &t, const std::vector<Constraint> &cs);
+// the non-trivial columns of a FastTree -constraints matrix (ntax named rows of ncons chars '0' '1' '-') over `taxa` (search.cpp)
+std::vector<Constraint> constraints_for(const std::vector<std::string> &taxa, int ncons, int ntax, const char *const *names, const char *const *rows);
+
+// The candidate regraft edges of one SPR prune, in the order the search scores them (search.cpp spr_round and the door
+// pml_debug_spr_enumerate share this one function).  The prune (p, ks) cuts the subtree behind p's neighbour s = nbr[p][ks]
+// off; p's other neighbours x, y (slot order) are joined.  From each inner end of the joined edge (x first) the pruned tree is
+// walked depth first, children in slot order; an edge (g, h), h away from the pruning point, has `distance` = the number of
+// edges from the joined edge to it, itself included.  Candidates are the edges with rmin <= distance <= rmax; a tip edge is a
+// candidate and is not descended.  Constraints: an edge whose far-side leaves joined with the pruned leaves are incompatible
+// with a constrained split is no candidate, and nothing behind it is.
+// steps = the path CLVs (towards the candidate, one per depth) that have to be built before this candidate and after the
+// previous one: depth 0 joins the far end `from` of the joined edge (length tx + ty) with `sib` across `at`; depth d > 0
+// carries the path CLV of depth d - 1 across (from, at) and joins it with `sib`.
+struct SprStep { int depth, from, at, sib; };
+// chain = all `distance` path CLVs from the joined edge to this candidate (what builds its path CLV from nothing)
+struct SprCandidate { int g, h, distance; std::vector<SprStep> steps, chain; };
+void spr_candidates(const Tree &T, const std::vector<Constraint> &cons, int p, int ks, int rmin, int rmax, std::vector<SprCandidate> &out);
 
 // NJ start tree; with constraints only joins whose cluster is compatible with every split are made
 Tree nj_tree(const EncodedAlignment &a, const std::vector<Constraint> *cons = nullptr);

@@ -13,6 +13,7 @@
 // node, re-optimise lightly (<= 2 smoothing passes), fall back to the single best move if the
 // combination did not improve, and to no move if that fails too.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,26 +52,29 @@ void nni_apply(Tree &T, int u, int v, int alt, double tnew) {
 
 // FastTree -constraints semantics (FastTreeRunner.java:54-64, 243-273): every 0/1 column is a split
 // the result must display; taxa the matrix does not name, or marks '-', are free in that column
+std::vector<Constraint> constraints_for(const std::vector<std::string> &taxa, int ncons, int ntax, const char *const *names, const char *const *rows) {
+    std::vector<Constraint> out;
+    const int n = (int)taxa.size(), words = (n + 63) / 64;
+    std::vector<int> map(ntax, -1);
+    for (int i = 0; i < ntax; ++i) for (int t = 0; t < n; ++t) if (taxa[t] == names[i]) { map[i] = t; break; }
+    for (int c = 0; c < ncons; ++c) {
+        Constraint K; K.one.assign(words, 0); K.zero.assign(words, 0);
+        int n1 = 0, n0 = 0;
+        for (int i = 0; i < ntax; ++i) {
+            const int t = map[i]; if (t < 0) continue;
+            if (rows[i][c] == '1') { K.one[t >> 6] |= 1ULL << (t & 63); ++n1; }
+            else if (rows[i][c] == '0') { K.zero[t >> 6] |= 1ULL << (t & 63); ++n0; }
+        }
+        if (n1 >= 2 && n0 >= 2) out.push_back(K);        // smaller sides are trivially displayed
+    }
+    return out;
+}
 int Batch::set_constraints(int ncons, int ntax, const char *const *names, const char *const *rows) {
     for (Gene &G : genes) G.cons.clear();
     if (ncons <= 0 || ntax <= 0) return 0;
     if (!names || !rows) return ctx->fail(-1, "constraint matrix missing");
     for (int i = 0; i < ntax; ++i) if (!names[i] || !rows[i] || (int)strnlen(rows[i], (size_t)ncons) < ncons) return ctx->fail(-1, "constraint row shorter than nconstraints");
-    for (Gene &G : genes) {
-        const int n = G.aln.ntax, words = (n + 63) / 64;
-        std::vector<int> map(ntax, -1);
-        for (int i = 0; i < ntax; ++i) for (int t = 0; t < n; ++t) if (G.aln.names[t] == names[i]) { map[i] = t; break; }
-        for (int c = 0; c < ncons; ++c) {
-            Constraint K; K.one.assign(words, 0); K.zero.assign(words, 0);
-            int n1 = 0, n0 = 0;
-            for (int i = 0; i < ntax; ++i) {
-                const int t = map[i]; if (t < 0) continue;
-                if (rows[i][c] == '1') { K.one[t >> 6] |= 1ULL << (t & 63); ++n1; }
-                else if (rows[i][c] == '0') { K.zero[t >> 6] |= 1ULL << (t & 63); ++n0; }
-            }
-            if (n1 >= 2 && n0 >= 2) G.cons.push_back(K);        // smaller sides are trivially displayed
-        }
-    }
+    for (Gene &G : genes) G.cons = constraints_for(G.aln.names, ncons, ntax, names, rows);
     return 0;
 }
 
@@ -359,13 +363,13 @@ constexpr int SPR_MAX_RADIUS = 6;
 constexpr int SPR_INS_SLOT = 7;
 constexpr size_t SPR_UNIT_BUDGET = 96;
 struct PathOp { int depth; Side left; double tl; int lbv, lbq; Side right; double tr; int rbv, rbq; };
-struct Unit { std::vector<PathOp> paths; int g, h, mslot; };   // score candidate edge (g,h) with path slot mslot
+struct Unit { std::vector<PathOp> paths; int g, h, mslot, dist; };   // score candidate edge (g,h) with path slot mslot
 struct Prune { int p, ks, s, x, y; double tx, ty, ts; std::vector<Unit> units; size_t rbase; };
 struct SprState {
     int p = 0, ks = 0; bool done = false;        // cursor: next prune to build
     std::vector<Prune> batch; size_t bi = 0;      // scored prunes waiting to be read, bi = next to read
     int phase = -1;                               // -1: needs scores; 0: scores in flight; 1..5: applying batch[bi]
-    double best = -1e300; int bg = -1, bh = -1;
+    double best = -1e300; int bg = -1, bh = -1, bdist = 0;
     Tree backup;
 };
 void spr_apply(Tree &T, int p, int x, int y, int g, int h) {
@@ -377,72 +381,107 @@ void spr_apply(Tree &T, int p, int x, int y, int g, int h) {
     T.nbr[g][sg] = p; T.len[g][sg] = 0.5 * tgh; T.nbr[h][sh] = p; T.len[h][sh] = 0.5 * tgh;
     T.nbr[p][kx] = g; T.len[p][kx] = 0.5 * tgh; T.nbr[p][ky] = h; T.len[p][ky] = 0.5 * tgh;
 }
+// the prune (p, ks) of gene g with its candidates as launchable units
+void prune_units(const Batch &B, int g, int p, int ks, int rmin, int rmax, std::vector<SprCandidate> &cands, Prune &P) {
+    const Tree &T = B.genes[g].tree;
+    P.p = p; P.ks = ks; P.s = T.nbr[p][ks];
+    int xy[2]; double lxy[2]; others(T, p, P.s, xy, lxy);
+    P.x = xy[0]; P.y = xy[1]; P.tx = lxy[0]; P.ty = lxy[1]; P.ts = T.len[p][ks];
+    P.units.clear();
+    spr_candidates(T, B.genes[g].cons, p, ks, rmin, rmax, cands);
+    for (const SprCandidate &c : cands) {
+        Unit u; u.g = c.g; u.h = c.h; u.mslot = c.distance - 1; u.dist = c.distance;
+        for (const SprStep &sp : c.steps) {
+            const int ks_sib = T.slot(sp.at, sp.sib);
+            if (sp.depth == 0) u.paths.push_back({0, B.msg(g, sp.from, p), P.tx + P.ty, -1, 0, B.msg(g, sp.sib, sp.at), T.len[sp.at][ks_sib], sp.at, ks_sib});
+            else { const int kf = T.slot(sp.from, sp.at);
+                   u.paths.push_back({sp.depth, {SIDE_SCRATCH, sp.depth - 1}, T.len[sp.from][kf], sp.from, kf, B.msg(g, sp.sib, sp.at), T.len[sp.at][ks_sib], sp.at, ks_sib}); }
+        }
+        P.units.push_back(std::move(u));
+    }
+}
+// what scores the candidates of gene g's prunes `batch` in one launch: the cached messages they read, then per candidate
+// its path CLVs, the insertion CLV (slot ins) and the evaluation across the pendant branch that consumes it
+void emit_scores(Batch &B, int g, std::vector<Prune> &batch, int ins, std::vector<PendingOp> &ops, std::vector<Batch::Tail> &tails,
+                 std::vector<size_t> &pool_off, size_t &pool_bytes, size_t &nres) {
+    const Gene &G = B.genes[g]; const Tree &T = G.tree;
+    auto need_side = [&](const Side &sd) {
+        if (sd.kind != SIDE_MSG) return;
+        const int v = G.aln.ntax + sd.id / 3, to = T.nbr[v][sd.id % 3];
+        B.need(g, v, to, ops);
+    };
+    // every cached message the batch reads, first
+    for (const Prune &P : batch) {
+        need_side(B.msg(g, P.s, P.p));
+        for (const Unit &u : P.units) {
+            for (const PathOp &po : u.paths) { need_side(po.left); need_side(po.right); }
+            need_side(B.msg(g, u.h, u.g));
+        }
+    }
+    int count = 0;
+    for (size_t q = 0; q < ops.size(); ++q) if (ops[q].gene == g) ++count;
+    const size_t pl_bytes = ((size_t)G.aln.mpad * 8 + 255) / 256 * 256;
+    for (Prune &P : batch) {
+        const Side sp = B.msg(g, P.s, P.p);
+        P.rbase = nres;
+        for (const Unit &u : P.units) {
+            for (const PathOp &po : u.paths) {
+                PendingOp o; o.gene = g; o.out_kind = SIDE_SCRATCH; o.out_id = po.depth; o.level = 0;
+                o.child[0] = po.left; o.t[0] = po.tl; o.bv[0] = po.lbv; o.bq[0] = po.lbq;
+                o.child[1] = po.right; o.t[1] = po.tr; o.bv[1] = po.rbv; o.bq[1] = po.rbq;
+                ops.push_back(o); ++count;
+            }
+            const double tgh = T.len[u.g][T.slot(u.g, u.h)];
+            PendingOp I; I.gene = g; I.out_kind = SIDE_SCRATCH; I.out_id = ins; I.level = 0;
+            I.transient = true;                        // read by the evaluation right behind it and by nothing else
+            I.child[0] = {SIDE_SCRATCH, u.mslot}; I.t[0] = 0.5 * tgh; I.child[1] = B.msg(g, u.h, u.g); I.t[1] = 0.5 * tgh;
+            ops.push_back(I); ++count;
+            Batch::Tail t{g, sp, {SIDE_SCRATCH, ins}, MODE_EVALUATE, P.ts, 0, 0, count};
+            t.bv = P.p; t.bq = P.ks;                   // the pendant branch: one matrix set for all its candidates
+            pool_off.push_back(pool_bytes); pool_bytes += pl_bytes; ++nres;
+            tails.push_back(t);
+        }
+    }
+}
+constexpr int THOROUGH_PARTS = 8;      // thorough insertions of one gene in flight: three scratch CLVs each (NSCRATCH = 24)
+constexpr int THOROUGH_SWEEPS = 8;
+// indices of the `top` best lazy scores, best first, equals in candidate order (top < 0: all)
+std::vector<int> top_candidates(const std::vector<double> &lazy, int top) {
+    std::vector<int> idx(lazy.size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int)i;
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return lazy[a] > lazy[b]; });
+    if (top >= 0 && (size_t)top < idx.size()) idx.resize(top);
+    return idx;
+}
+// the thorough insertion of candidate c of prune (p, ks), from the lengths the lazy score uses
+ThoroughJob thorough_job(const Tree &T, int g, int p, int ks, const SprCandidate &c) {
+    const double tgh = T.len[c.g][T.slot(c.g, c.h)];
+    return ThoroughJob{g, p, ks, c, T.len[p][ks], 0.5 * tgh, 0.5 * tgh, -1e300, 0};
+}
 }  // namespace
 
 int Batch::spr_round(const std::vector<char> &active, int radius, std::vector<double> &lnl, std::vector<int> &moves) {
+    return spr_round_windowed(active, std::vector<int>(genes.size(), std::min(radius, SPR_MAX_RADIUS)), 1, lnl, moves, nullptr);
+}
+
+int Batch::spr_round_windowed(const std::vector<char> &active, const std::vector<int> &radius_of, int rmin, std::vector<double> &lnl,
+                              std::vector<int> &moves, std::vector<SearchTrace> *trace) {
     const int n = (int)genes.size();
     ++topo_epoch;
     moves.assign(n, 0);
-    radius = std::min(radius, SPR_MAX_RADIUS);
+    // path CLVs live in scratch slots 0 .. radius - 1 (one per depth), the insertion CLV behind them
+    std::vector<int> radius(n), ins_slot(n);
+    for (int g = 0; g < n; ++g) { radius[g] = std::max(0, std::min(radius_of[g], genes[g].nscratch - 2)); ins_slot[g] = std::max(SPR_INS_SLOT, radius[g]); }
     std::vector<SprState> st(n);
     std::vector<std::vector<double>> scores_of(n);      // per gene: candidate scores of its current batch (Prune::rbase indexes it)
-    for (int g = 0; g < n; ++g) { st[g].done = !active[g] || genes[g].aln.ntax < 5; st[g].p = genes[g].aln.ntax; st[g].ks = 0; st[g].phase = -1; }
+    for (int g = 0; g < n; ++g) { st[g].done = !active[g] || genes[g].aln.ntax < 5 || radius[g] < rmin; st[g].p = genes[g].aln.ntax; st[g].ks = 0; st[g].phase = -1; }
 
-    // the unit list of the prune (p, ks) of gene g (DFS order of the oracle's recursion)
-    auto build_prune = [&](int g, int p, int ks, Prune &P) {
-        const Tree &T = genes[g].tree; const int nt = T.ntax;
-        P.p = p; P.ks = ks; P.s = T.nbr[p][ks];
-        int xy[2]; double lxy[2]; others(T, p, P.s, xy, lxy);
-        P.x = xy[0]; P.y = xy[1]; P.tx = lxy[0]; P.ty = lxy[1]; P.ts = T.len[p][ks];
-        P.units.clear();
-        std::vector<PathOp> pending;
-        // constraints: regrafting beyond edge (gg,h) turns its split into L(h side) + L(S); if that is
-        // incompatible, neither this edge nor anything behind it is a candidate
-        const std::vector<Constraint> &cons = genes[g].cons;
-        std::vector<std::vector<uint64_t>> leafs; std::vector<uint64_t> LS;
-        if (!cons.empty()) {
-            leafs = leaf_sets(T);
-            LS.assign((nt + 63) / 64, 0);
-            if (P.s < nt) LS[P.s >> 6] |= 1ULL << (P.s & 63); else LS = leafs[(P.s - nt) * 3 + T.slot(P.s, p)];
-        }
-        auto allowed = [&](int gg, int h) {
-            if (cons.empty()) return true;
-            std::vector<uint64_t> X((nt + 63) / 64, 0);
-            if (h < nt) X[h >> 6] |= 1ULL << (h & 63); else X = leafs[(h - nt) * 3 + T.slot(h, gg)];
-            for (size_t w = 0; w < X.size(); ++w) X[w] |= LS[w];
-            return compatible_with_all(cons, X);
-        };
-        std::function<void(int, int, int)> explore = [&](int gg, int h, int depth) {
-            if (!allowed(gg, h)) { pending.clear(); return; }
-            Unit u; u.paths = pending; pending.clear(); u.g = gg; u.h = h; u.mslot = depth - 1;
-            P.units.push_back(u);
-            if (h < nt || depth >= radius) return;
-            int ch[2]; double lc[2]; others(T, h, gg, ch, lc);
-            const double tgh = T.len[gg][T.slot(gg, h)];
-            for (int i = 0; i < 2; ++i) {
-                pending.push_back({depth, {SIDE_SCRATCH, depth - 1}, tgh, gg, T.slot(gg, h), msg(g, ch[1 - i], h), lc[1 - i], h, T.slot(h, ch[1 - i])});
-                explore(h, ch[i], depth + 1);
-            }
-        };
-        for (int sidei = 0; sidei < 2; ++sidei) {
-            const int a = sidei == 0 ? P.x : P.y, b = sidei == 0 ? P.y : P.x;
-            if (a < nt) continue;
-            int ch[2]; double lc[2]; others(T, a, p, ch, lc);
-            for (int i = 0; i < 2; ++i) {
-                pending.push_back({0, msg(g, b, p), P.tx + P.ty, -1, 0, msg(g, ch[1 - i], a), lc[1 - i], a, T.slot(a, ch[1 - i])});
-                explore(a, ch[i], 1);
-            }
-        }
-    };
+    // the unit list of the prune (p, ks) of gene g (DFS order of the oracle's recursion: host.cpp spr_candidates)
+    std::vector<SprCandidate> cands;
+    auto build_prune = [&](int g, int p, int ks, Prune &P) { prune_units(*this, g, p, ks, rmin, radius[g], cands, P); };
     auto cursor_next = [&](int g) {
         SprState &S = st[g];
         if (++S.ks == 3) { S.ks = 0; ++S.p; }
-    };
-    auto need_side = [&](int g, const Side &sd, std::vector<PendingOp> &ops) {
-        if (sd.kind != SIDE_MSG) return;
-        const Gene &G = genes[g];
-        const int v = G.aln.ntax + sd.id / 3, to = G.tree.nbr[v][sd.id % 3];
-        need(g, v, to, ops);
     };
     // which branch the gene optimises in apply phase ph of prune P (oracle order)
     auto apply_edge = [&](const SprState &S, int ph, int &u, int &v) {
@@ -474,38 +513,7 @@ int Batch::spr_round(const std::vector<char> &active, int radius, std::vector<do
                 }
                 if (S.batch.empty()) { S.done = true; continue; }
                 S.phase = 0;
-                // every cached message the batch reads, first
-                for (const Prune &P : S.batch) {
-                    need_side(g, msg(g, P.s, P.p), ops);
-                    for (const Unit &u : P.units) {
-                        for (const PathOp &po : u.paths) { need_side(g, po.left, ops); need_side(g, po.right, ops); }
-                        need_side(g, msg(g, u.h, u.g), ops);
-                    }
-                }
-                int count = 0;
-                for (size_t q = 0; q < ops.size(); ++q) if (ops[q].gene == g) ++count;
-                const size_t pl_bytes = ((size_t)genes[g].aln.mpad * 8 + 255) / 256 * 256;
-                for (Prune &P : S.batch) {
-                    const Side sp = msg(g, P.s, P.p);
-                    P.rbase = nres;
-                    for (const Unit &u : P.units) {
-                        for (const PathOp &po : u.paths) {
-                            PendingOp o; o.gene = g; o.out_kind = SIDE_SCRATCH; o.out_id = po.depth; o.level = 0;
-                            o.child[0] = po.left; o.t[0] = po.tl; o.bv[0] = po.lbv; o.bq[0] = po.lbq;
-                            o.child[1] = po.right; o.t[1] = po.tr; o.bv[1] = po.rbv; o.bq[1] = po.rbq;
-                            ops.push_back(o); ++count;
-                        }
-                        const double tgh = T.len[u.g][T.slot(u.g, u.h)];
-                        PendingOp I; I.gene = g; I.out_kind = SIDE_SCRATCH; I.out_id = SPR_INS_SLOT; I.level = 0;
-                        I.transient = true;                        // read by the evaluation right behind it and by nothing else
-                        I.child[0] = {SIDE_SCRATCH, u.mslot}; I.t[0] = 0.5 * tgh; I.child[1] = msg(g, u.h, u.g); I.t[1] = 0.5 * tgh;
-                        ops.push_back(I); ++count;
-                        Tail t{g, sp, {SIDE_SCRATCH, SPR_INS_SLOT}, MODE_EVALUATE, P.ts, 0, 0, count};
-                        t.bv = P.p; t.bq = P.ks;                   // the pendant branch: one matrix set for all its candidates
-                        pool_off.push_back(pool_bytes); pool_bytes += pl_bytes; ++nres;
-                        tails.push_back(t);
-                    }
-                }
+                emit_scores(*this, g, S.batch, ins_slot[g], ops, tails, pool_off, pool_bytes, nres);
                 kind[g] = 0;
             } else if (S.phase >= 1 && S.phase <= 4) {
                 int u, v; apply_edge(S, S.phase, u, v);
@@ -553,6 +561,7 @@ int Batch::spr_round(const std::vector<char> &active, int radius, std::vector<do
                 if (r0 > lnl[g] + 1e-6) {
                     // kept: the tree changed, so the scores of the later prunes of this batch are void -- resume
                     // right behind this prune, on the new tree
+                    if (trace) (*trace)[g].steps.push_back({1, rmin, radius[g], S.bdist, lnl[g], r0, T.newick(genes[g].aln.names, 12)});
                     lnl[g] = r0; moves[g]++;
                     const Prune &P = S.batch[S.bi];
                     S.p = P.p; S.ks = P.ks; cursor_next(g);
@@ -570,7 +579,7 @@ int Batch::spr_round(const std::vector<char> &active, int radius, std::vector<do
                 S.best = -1e300; S.bg = S.bh = -1;
                 for (size_t k = 0; k < P.units.size(); ++k) {
                     const double sc = scores_of[g][P.rbase + k];
-                    if (sc > S.best) { S.best = sc; S.bg = P.units[k].g; S.bh = P.units[k].h; }
+                    if (sc > S.best) { S.best = sc; S.bg = P.units[k].g; S.bh = P.units[k].h; S.bdist = P.units[k].dist; }
                 }
                 if (S.bg >= 0 && S.best > lnl[g] + SPR_MIN_GAIN) {
                     S.backup = T;
@@ -638,6 +647,343 @@ int Batch::search(bool nni, int spr_radius, bool opt_alpha_flag, double eps, dou
                        host_phase_ms[HP_NNI_RUN], host_phase_ms[HP_NNI_SELECT], host_phase_ms[HP_ALPHA_HOST], host_phase_ms[HP_RUN_SYNCED]);
     for (int g = 0; g < n; ++g) lnl_out[g] = lnl[g];
     for (int g = 0; g < n; ++g) if (!tree_displays(genes[g].tree, genes[g].cons)) return ctx->fail(-5, "internal: result violates the topological constraints");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// RAxML's schedule (peprml.h pml_search2): the start and the end are search()'s; in between the rearrangement
+// radius is either given (honoured as far as the batch's scratch CLVs reach: search2 batches are created with enough) or
+// determined per gene on the start tree, and the fast phase is search()'s outer loop with the gene's radius.  Every gene
+// takes its decisions alone and advances in lockstep with the others, as in search().
+// ------------------------------------------------------------------------------------------
+int Batch::search2(const Search2Opts &o, double *lnl_out, std::vector<SearchTrace> *trace) {
+    const int n = (int)genes.size();
+    std::vector<double> lnl(n, 0.0);
+    for (int g = 0; g < n; ++g) {         // a start tree that violates the constraints is replaced by a constrained NJ tree
+        Gene &G = genes[g];
+        if (!G.cons.empty() && !tree_displays(G.tree, G.cons)) { G.tree = nj_tree(G.aln, &G.cons); invalidate_all(g); ++topo_epoch; }
+    }
+    newton_tol = 1e-6;
+    struct Restore { double &r; ~Restore() { r = 1e-8; } } restore{newton_tol};
+    if (int rc = optimize(o.opt_alpha, 0.1, lnl.data())) return rc;
+    rates_on = false;
+    struct RatesBack { bool &r; ~RatesBack() { r = true; } } rates_back{rates_on};
+    if (trace) { trace->assign(n, SearchTrace()); for (int g = 0; g < n; ++g) (*trace)[g].lnl_start = lnl[g]; }
+    std::vector<int> radius(n, o.radius);
+    if (o.radius_auto) {
+        // radius determination: from a copy of the start tree T0 one lazy SPR round at r = step, 2 step, ... then a coarse
+        // optimisation; a gene stops after the first r that does not beat its best so far (L0 counts) and goes on from the
+        // tree of its first maximum
+        struct Saved { Tree tree; double alpha, lnl; };
+        std::vector<Saved> t0(n), best(n);
+        for (int g = 0; g < n; ++g) { t0[g] = Saved{genes[g].tree, genes[g].alpha, lnl[g]}; best[g] = t0[g]; }
+        auto put = [&](int g, const Saved &sv) { genes[g].tree = sv.tree; if (genes[g].alpha != sv.alpha) set_alpha(g, sv.alpha); invalidate_all(g); lnl[g] = sv.lnl; };
+        std::vector<char> trying(n, 1);
+        std::fill(radius.begin(), radius.end(), o.radius_step);
+        for (int r = o.radius_step; r <= o.radius_max; r += o.radius_step) {
+            bool any = false; for (char a : trying) any |= a;
+            if (!any) break;
+            for (int g = 0; g < n; ++g) if (trying[g]) put(g, t0[g]);
+            std::vector<int> mv;
+            if (int rc = spr_round_windowed(trying, std::vector<int>(n, r), 1, lnl, mv, nullptr)) return rc;
+            if (int rc = optimize(o.opt_alpha, 0.1, lnl.data(), &trying)) return rc;
+            for (int g = 0; g < n; ++g) {
+                if (!trying[g]) continue;
+                if (trace) { (*trace)[g].trial_radius.push_back(r); (*trace)[g].trial_lnl.push_back(lnl[g]); }
+                if (lnl[g] > best[g].lnl) { best[g] = Saved{genes[g].tree, genes[g].alpha, lnl[g]}; radius[g] = r; }
+                else trying[g] = 0;
+            }
+        }
+        for (int g = 0; g < n; ++g) put(g, best[g]);
+        ++topo_epoch;
+    }
+    if (trace) for (int g = 0; g < n; ++g) (*trace)[g].radius_chosen = radius[g];
+    bool any_spr = false; for (int r : radius) any_spr |= r > 0;
+    std::vector<char> active(n, (o.nni || any_spr) ? 1 : 0);
+    for (int outer = 0; outer < 20; ++outer) {
+        bool any = false; for (char a : active) any |= a;
+        if (!any) break;
+        std::vector<int> moves(n, 0), applied;
+        std::vector<char> ract(active);
+        for (int round = 0; o.nni && round < 100; ++round) {      // (search() runs these whatever its nni flag says once it has a radius)
+            bool anyr = false; for (char a : ract) anyr |= a;
+            if (!anyr) break;
+            const std::vector<double> before(lnl);
+            if (int rc = nni_round(ract, lnl, applied)) return rc;
+            for (int g = 0; g < n; ++g) if (ract[g]) {
+                if (applied[g] == 0) { ract[g] = 0; continue; }
+                moves[g] += applied[g];
+                if (trace) (*trace)[g].steps.push_back({0, 0, 0, 0, before[g], lnl[g], genes[g].tree.newick(genes[g].aln.names, 12)});
+            }
+        }
+        if (any_spr) {
+            std::vector<char> sact(active);
+            std::vector<int> smoves;
+            for (int round = 0; round < 10; ++round) {
+                bool anys = false; for (char a : sact) anys |= a;
+                if (!anys) break;
+                if (int rc = spr_round_windowed(sact, radius, 1, lnl, smoves, trace)) return rc;
+                for (int g = 0; g < n; ++g) if (sact[g]) { if (smoves[g] == 0) sact[g] = 0; else moves[g] += smoves[g]; }
+            }
+        }
+        if (int rc = optimize(o.opt_alpha, 0.1, lnl.data(), &active)) return rc;
+        for (int g = 0; g < n; ++g) if (active[g] && moves[g] == 0) active[g] = 0;
+    }
+    if (o.thorough) {
+        // windows [1, step], [step + 1, 2 step] ...: a cycle without an accepted move shifts a gene's window, one with a move
+        // resets it; the gene is done when the window would pass thorough_radius_max
+        std::vector<int> rmin(n, 1), rmax(n, o.radius_step), mv;
+        std::vector<char> tact(n, 1);
+        for (int g = 0; g < n; ++g) if (genes[g].aln.ntax < 5 || rmax[g] > o.thorough_radius_max) tact[g] = 0;
+        for (int cycle = 0; cycle < 1000; ++cycle) {
+            bool any = false; for (char a : tact) any |= a;
+            if (!any) break;
+            if (int rc = thorough_cycle(tact, rmin, rmax, o.thorough_top, lnl, mv, trace)) return rc;
+            for (int g = 0; g < n; ++g) {
+                if (!tact[g]) continue;
+                if (mv[g] > 0) { rmin[g] = 1; rmax[g] = o.radius_step; }
+                else { rmin[g] += o.radius_step; rmax[g] += o.radius_step; if (rmax[g] > o.thorough_radius_max) tact[g] = 0; }
+            }
+        }
+    }
+    newton_tol = 1e-8;
+    rates_on = true;
+    if (int rc = optimize(o.opt_alpha, o.eps, lnl.data())) return rc;
+    for (int g = 0; g < n; ++g) lnl_out[g] = lnl[g];
+    for (int g = 0; g < n; ++g) if (!tree_displays(genes[g].tree, genes[g].cons)) return ctx->fail(-5, "internal: result violates the topological constraints");
+    return 0;
+}
+
+int Batch::spr_scores(int p, int ks, int rmin, int rmax, int thorough_top, std::vector<SprCandidate> &cands, std::vector<double> &lazy,
+                      std::vector<std::array<double, 4>> &thorough) {
+    const Gene &G = genes[0]; const Tree &T = G.tree;
+    if (T.ntax < 5 || p < T.ntax || p >= T.nnodes() || ks < 0 || ks > 2 || rmin < 1 || rmax < rmin) return ctx->fail(-1, "bad prune or window");
+    if (rmax > G.nscratch - 2) return ctx->fail(-1, "window beyond the batch's SPR scratch CLVs");
+    std::vector<Prune> batch(1);
+    prune_units(*this, 0, p, ks, rmin, rmax, cands, batch[0]);
+    lazy.assign(cands.size(), 0.0);
+    const double nan = std::nan("");
+    thorough.assign(cands.size(), {nan, nan, nan, nan});
+    if (cands.empty()) return 0;
+    std::vector<PendingOp> ops; std::vector<Tail> tails; std::vector<size_t> pool_off; size_t pool_bytes = 0, nres = 0;
+    emit_scores(*this, 0, batch, std::max(SPR_INS_SLOT, rmax), ops, tails, pool_off, pool_bytes, nres);
+    if (int rc = ensure_tailpool(pool_bytes)) return rc;
+    if (int rc = ensure_results(nres)) return rc;
+    for (size_t k = 0; k < tails.size(); ++k) {
+        tails[k].patlnl_dev = reinterpret_cast<double *>(d_tailpool + pool_off[k]);
+        tails[k].result_dev = d_chain + 4 * k; tails[k].result_host = h_chain + 4 * k;
+    }
+    if (int rc = run(ops, tails)) return rc;
+    for (size_t k = 0; k < nres; ++k) lazy[k] = h_chain[4 * k];
+    if (thorough_top == 0) return 0;
+    const double save_tol = newton_tol; newton_tol = 1e-6;            // the search's tolerance while the topology moves
+    struct Restore { double &r; double v; ~Restore() { r = v; } } restore{newton_tol, save_tol};
+    std::vector<ThoroughJob> jobs;
+    const std::vector<int> top = top_candidates(lazy, thorough_top);
+    for (int k : top) jobs.push_back(thorough_job(T, 0, p, ks, cands[k]));
+    if (int rc = thorough_insert(jobs)) return rc;
+    for (size_t i = 0; i < top.size(); ++i) thorough[top[i]] = {jobs[i].score, jobs[i].ts, jobs[i].tg, jobs[i].th};
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Thorough insertion.  A job owns one part of its gene's launch and three scratch CLVs: two that the path CLVs of its
+// candidate alternate between (the last one stays: G, the pruned tree seen from the candidate edge's near end) and one for the
+// CLV the Newton at hand needs.  With S the pruned subtree's message and H the far end's:
+//   pendant branch ts:  S  against  G(tg) x H(th)
+//   near half     tg:  G  against  S(ts) x H(th)
+//   far half      th:  H  against  S(ts) x G(tg)
+// one launch set per Newton for all jobs of all genes, results read by the host in between (each Newton starts from the
+// lengths the previous ones found: Gauss-Seidel).  No new kernel: these are nni_round's launch shapes.
+// ------------------------------------------------------------------------------------------
+int Batch::thorough_insert(std::vector<ThoroughJob> &jobs) {
+    const int n = (int)genes.size();
+    {   // every cached message the jobs read, in a launch of their own: parts must not depend on each other
+        std::vector<PendingOp> ops;
+        auto need_msg = [&](int g, int node, int toward) { if (msg(g, node, toward).kind == SIDE_MSG) need(g, node, toward, ops); };
+        for (const ThoroughJob &J : jobs) {
+            const Tree &T = genes[J.g].tree;
+            need_msg(J.g, T.nbr[J.p][J.ks], J.p); need_msg(J.g, J.cand.h, J.cand.g);
+            for (const SprStep &st : J.cand.chain) { if (st.depth == 0) need_msg(J.g, st.from, J.p); need_msg(J.g, st.sib, st.at); }
+        }
+        if (!ops.empty()) { std::vector<Tail> none; if (int rc = run(ops, none)) return rc; }
+    }
+    std::vector<int> seen(n, 0), part(jobs.size());
+    int nchunks = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) { part[j] = seen[jobs[j].g]++; nchunks = std::max(nchunks, part[j] / THOROUGH_PARTS + 1); jobs[j].sweeps = 0; jobs[j].score = -1e300; }
+    for (int c = 0; c < nchunks; ++c) {
+        std::vector<size_t> mine, live;
+        for (size_t j = 0; j < jobs.size(); ++j) if (part[j] / THOROUGH_PARTS == c) mine.push_back(j);
+        live = mine;
+        // stage 0..2: Newton on ts, tg, th; stage 3: the evaluation
+        auto launch = [&](int stage, bool with_chain, const std::vector<size_t> &who, std::vector<double> &r0) -> int {
+            std::vector<PendingOp> ops; std::vector<Tail> tails; std::vector<size_t> off; size_t bytes = 0;
+            std::vector<int> count((size_t)n * THOROUGH_PARTS, 0);
+            for (size_t j : who) {
+                const ThoroughJob &J = jobs[j];
+                const int g = J.g, pt = part[j] % THOROUGH_PARTS, sb = 3 * pt;
+                const Gene &G = genes[g]; const Tree &T = G.tree;
+                if (sb + 2 >= G.nscratch) return ctx->fail(-5, "internal: thorough insertion beyond the scratch CLVs");
+                int xy[2]; double lxy[2]; others(T, J.p, T.nbr[J.p][J.ks], xy, lxy);
+                const Side S = msg(g, T.nbr[J.p][J.ks], J.p), H = msg(g, J.cand.h, J.cand.g);
+                const Side Gs{SIDE_SCRATCH, sb + ((J.cand.distance - 1) & 1)}, Bs{SIDE_SCRATCH, sb + 2};
+                int &cnt = count[(size_t)g * THOROUGH_PARTS + pt];
+                if (with_chain) for (size_t k = 0; k < J.cand.chain.size(); ++k) {
+                    const SprStep &st = J.cand.chain[k];
+                    PendingOp o; o.gene = g; o.part = pt; o.out_kind = SIDE_SCRATCH; o.out_id = sb + (int)(k & 1); o.level = 0;
+                    if (k == 0) { o.child[0] = msg(g, st.from, J.p); o.t[0] = lxy[0] + lxy[1]; }
+                    else { const int kf = T.slot(st.from, st.at); o.child[0] = {SIDE_SCRATCH, sb + (int)((k - 1) & 1)}; o.t[0] = T.len[st.from][kf]; o.bv[0] = st.from; o.bq[0] = kf; }
+                    const int kq = T.slot(st.at, st.sib);
+                    o.child[1] = msg(g, st.sib, st.at); o.t[1] = T.len[st.at][kq]; o.bv[1] = st.at; o.bq[1] = kq;
+                    ops.push_back(o); ++cnt;
+                }
+                PendingOp B; B.gene = g; B.part = pt; B.out_kind = SIDE_SCRATCH; B.out_id = sb + 2; B.level = 0;
+                if (stage == 0 || stage == 3) { B.child[0] = Gs; B.t[0] = J.tg; B.child[1] = H; B.t[1] = J.th; }
+                else if (stage == 1) { B.child[0] = S; B.t[0] = J.ts; B.child[1] = H; B.t[1] = J.th; }
+                else { B.child[0] = S; B.t[0] = J.ts; B.child[1] = Gs; B.t[1] = J.tg; }
+                B.transient = stage == 3;
+                ops.push_back(B); ++cnt;
+                Tail t = stage == 0 ? Tail{g, S, Bs, MODE_SUMTABLE, J.ts, 32, 0, cnt} : stage == 1 ? Tail{g, Gs, Bs, MODE_SUMTABLE, J.tg, 32, 0, cnt}
+                       : stage == 2 ? Tail{g, H, Bs, MODE_SUMTABLE, J.th, 32, 0, cnt} : Tail{g, S, Bs, MODE_EVALUATE, J.ts, 0, 0, cnt};
+                t.part = pt;
+                off.push_back(bytes);
+                bytes += stage == 3 ? ((size_t)G.aln.mpad * 8 + 255) / 256 * 256 : (clv_doubles(G.aln.mpad) * 8 + (size_t)G.aln.mpad * 4 + 255) / 256 * 256;
+                tails.push_back(t);
+            }
+            if (int rc = ensure_tailpool(bytes)) return rc;
+            if (int rc = ensure_results(tails.size())) return rc;
+            for (size_t k = 0; k < tails.size(); ++k) {
+                if (stage == 3) tails[k].patlnl_dev = reinterpret_cast<double *>(d_tailpool + off[k]);
+                else tails[k].sumtab_dev = reinterpret_cast<double *>(d_tailpool + off[k]);
+                tails[k].result_dev = d_chain + 4 * k; tails[k].result_host = h_chain + 4 * k;
+            }
+            ++cnt_spr;
+            if (int rc = run(ops, tails)) return rc;
+            r0.resize(who.size());
+            for (size_t k = 0; k < who.size(); ++k) r0[k] = h_chain[4 * k];
+            return 0;
+        };
+        std::vector<double> r0;
+        for (int sweep = 0; sweep < THOROUGH_SWEEPS && !live.empty(); ++sweep) {
+            std::vector<double> moved(live.size(), 0.0);
+            for (int stage = 0; stage < 3; ++stage) {
+                if (int rc = launch(stage, sweep == 0 && stage == 0, live, r0)) return rc;
+                for (size_t k = 0; k < live.size(); ++k) {
+                    ThoroughJob &J = jobs[live[k]];
+                    double &t = stage == 0 ? J.ts : stage == 1 ? J.tg : J.th;
+                    moved[k] = std::max(moved[k], std::fabs(r0[k] - t)); t = r0[k];
+                }
+            }
+            std::vector<size_t> next;
+            for (size_t k = 0; k < live.size(); ++k) { jobs[live[k]].sweeps = sweep + 1; if (moved[k] > newton_tol) next.push_back(live[k]); }
+            live.swap(next);
+        }
+        if (int rc = launch(3, false, mine, r0)) return rc;
+        for (size_t k = 0; k < mine.size(); ++k) jobs[mine[k]].score = r0[k];
+    }
+    return 0;
+}
+
+// One cycle of the thorough phase.  Genes advance in lockstep, one prune each per turn: lazy scores of the candidates in the
+// gene's window, thorough insertion of the best `top` of them, and if the best thorough score beats the current likelihood
+// the move goes through spr_round's apply phases (four branch Newtons, kept only if the tree really improved) starting
+// from the three lengths the insertion found.
+int Batch::thorough_cycle(const std::vector<char> &active, const std::vector<int> &rmin, const std::vector<int> &rmax, int top,
+                          std::vector<double> &lnl, std::vector<int> &moves, std::vector<SearchTrace> *trace) {
+    const int n = (int)genes.size();
+    ++topo_epoch;
+    moves.assign(n, 0);
+    struct St { int p, ks; bool done; std::vector<Prune> batch; std::vector<SprCandidate> cands; std::vector<double> lazy; Tree backup; ThoroughJob best; bool applying; };
+    std::vector<St> st(n);
+    for (int g = 0; g < n; ++g) { st[g].p = genes[g].aln.ntax; st[g].ks = 0; st[g].done = !active[g] || genes[g].aln.ntax < 5; st[g].applying = false; }
+    for (;;) {
+        // lazy scores of the next prune of every gene
+        std::vector<PendingOp> ops; std::vector<Tail> tails; std::vector<size_t> pool_off; size_t pool_bytes = 0, nres = 0;
+        std::vector<char> scored(n, 0);
+        for (int g = 0; g < n; ++g) {
+            St &S = st[g];
+            if (S.done) continue;
+            const Tree &T = genes[g].tree;
+            const int hi = std::min(rmax[g], genes[g].nscratch - 2);
+            S.batch.assign(1, Prune());
+            while (S.p < T.nnodes()) {
+                if (hi >= rmin[g]) prune_units(*this, g, S.p, S.ks, rmin[g], hi, S.cands, S.batch[0]); else S.batch[0].units.clear();
+                if (++S.ks == 3) { S.ks = 0; ++S.p; }
+                if (!S.batch[0].units.empty()) break;
+            }
+            if (S.batch[0].units.empty()) { S.done = true; continue; }
+            emit_scores(*this, g, S.batch, std::max(SPR_INS_SLOT, hi), ops, tails, pool_off, pool_bytes, nres);
+            scored[g] = 1;
+        }
+        if (!nres) break;
+        ++cnt_spr;
+        if (int rc = ensure_tailpool(pool_bytes)) return rc;
+        if (int rc = ensure_results(nres)) return rc;
+        for (size_t k = 0; k < tails.size(); ++k) {
+            tails[k].patlnl_dev = reinterpret_cast<double *>(d_tailpool + pool_off[k]);
+            tails[k].result_dev = d_chain + 4 * k; tails[k].result_host = h_chain + 4 * k;
+        }
+        if (int rc = run(ops, tails)) return rc;
+        std::vector<ThoroughJob> jobs;
+        for (int g = 0; g < n; ++g) {
+            if (!scored[g]) continue;
+            St &S = st[g]; const Prune &P = S.batch[0];
+            S.lazy.resize(P.units.size());
+            for (size_t k = 0; k < P.units.size(); ++k) S.lazy[k] = h_chain[4 * (P.rbase + k)];
+            for (int k : top_candidates(S.lazy, top <= 0 ? -1 : top)) jobs.push_back(thorough_job(genes[g].tree, g, P.p, P.ks, S.cands[k]));
+        }
+        if (int rc = thorough_insert(jobs)) return rc;
+        // the best thorough score of each gene; apply it if it beats the current likelihood
+        std::vector<char> applying(n, 0); bool any = false;
+        for (int g = 0; g < n; ++g) st[g].best.score = -1e300;
+        for (const ThoroughJob &J : jobs) if (J.score > st[J.g].best.score) st[J.g].best = J;
+        for (int g = 0; g < n; ++g) {
+            if (!scored[g]) continue;
+            St &S = st[g]; const Prune &P = S.batch[0]; Tree &T = genes[g].tree;
+            if (!(S.best.score > lnl[g] + SPR_MIN_GAIN)) continue;
+            S.backup = T;
+            spr_apply(T, P.p, P.x, P.y, S.best.cand.g, S.best.cand.h);
+            T.set_len(P.p, P.s, S.best.ts); T.set_len(P.p, S.best.cand.g, S.best.tg); T.set_len(P.p, S.best.cand.h, S.best.th);
+            invalidate_all(g);
+            applying[g] = 1; any = true;
+        }
+        if (!any) continue;
+        for (int ph = 1; ph <= 5; ++ph) {
+            ops.clear(); tails.clear();
+            auto edge = [&](int g, int &u, int &v) {
+                const St &S = st[g]; const Prune &P = S.batch[0];
+                if (ph == 1) { u = P.p; v = P.s; } else if (ph == 2) { u = P.p; v = S.best.cand.g; }
+                else if (ph == 3) { u = P.p; v = S.best.cand.h; } else { u = P.x; v = P.y; }
+            };
+            for (int g = 0; g < n; ++g) {
+                if (!applying[g]) continue;
+                const Tree &T = genes[g].tree;
+                if (ph <= 4) {
+                    int u, v; edge(g, u, v);
+                    need(g, u, v, ops); need(g, v, u, ops);
+                    tails.push_back({g, msg(g, u, v), msg(g, v, u), MODE_SUMTABLE, T.len[u][T.slot(u, v)], 32});
+                } else {
+                    const int r = T.nbr[0][0];
+                    need(g, r, 0, ops);
+                    tails.push_back({g, msg(g, 0, r), msg(g, r, 0), MODE_EVALUATE, T.len[0][0], 0});
+                }
+            }
+            ++cnt_spr;
+            if (int rc = run(ops, tails)) return rc;
+            for (int g = 0; g < n; ++g) {
+                if (!applying[g]) continue;
+                Tree &T = genes[g].tree;
+                const double r0 = res(g)[0];
+                if (ph <= 4) {
+                    int u, v; edge(g, u, v);
+                    if (r0 != T.len[u][T.slot(u, v)]) { T.set_len(u, v, r0); branch_changed(g, u, v); }
+                } else if (r0 > lnl[g] + 1e-6) {
+                    if (trace) (*trace)[g].steps.push_back({2, rmin[g], rmax[g], st[g].best.cand.distance, lnl[g], r0, T.newick(genes[g].aln.names, 12)});
+                    lnl[g] = r0; moves[g]++;
+                } else { T = st[g].backup; invalidate_all(g); }
+            }
+        }
+    }
     return 0;
 }
 

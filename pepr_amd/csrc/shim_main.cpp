@@ -140,6 +140,7 @@ int main(int argc, char **argv) {
     const char *tool = "raxmlHPC";
     std::string f = "d", model_s = "PROTGAMMAWAG", aln_f, run, tree_f, trees_f;
     bool pars_only = false; unsigned seed = 12345; unsigned long long bs_seed = 12345; int bs_reps = 0;
+    int radius_i = 0;                                      // -i: the rearrangement radius (0 = not given)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&](std::string &dst) { if (i + 1 >= argc) return false; dst = argv[++i]; return true; };
@@ -152,11 +153,25 @@ int main(int argc, char **argv) {
         else if (a == "-z") { if (!val(trees_f)) return fail(tool, "-z needs a value"); }
         else if (a == "-T") { if (!val(dummy)) return fail(tool, a + " needs a value"); }
         else if (a == "-p") { if (!val(dummy)) return fail(tool, a + " needs a value"); seed = (unsigned)std::strtoul(dummy.c_str(), nullptr, 10); }
+        else if (a == "-i") {                              // RAxML's initial rearrangement setting: a fixed radius, honoured as given
+            if (!val(dummy)) return fail(tool, "-i needs a value");
+            char *e = nullptr; const long r = std::strtol(dummy.c_str(), &e, 10);
+            if (dummy.empty() || *e || r < 1 || r > PML_SPR_RADIUS_MAX) return fail(tool, "-i needs a rearrangement radius 1.." + std::to_string(PML_SPR_RADIUS_MAX) + ", got " + dummy);
+            radius_i = (int)r;
+        }
         else if (a == "-y") pars_only = true;              // RAxMLRunner.java:134-140,241-251: parsimony start tree only
         else if (a == "-Y") return fail(tool, "parsimony bootstrap (-Y -N) is not built");
         else if (a == "-x") { if (!val(dummy)) return fail(tool, "-x needs a value"); bs_seed = std::strtoull(dummy.c_str(), nullptr, 10); }
         else if (a == "-N" || a == "-#") { if (!val(dummy)) return fail(tool, a + " needs a value"); bs_reps = std::atoi(dummy.c_str()); }
         else return fail(tool, "unknown option " + a);
+    }
+    // PEPRML_SEARCH_SCHEDULE=raxml: RAxML's schedule for -f d (radius determined on the start tree unless -i gives it, then the
+    // thorough phase).  A
+    // stock pepr.jar cannot pass flags to the tool it spawns, hence the environment; the library never reads it.
+    bool schedule_raxml = false;
+    if (const char *sch = std::getenv("PEPRML_SEARCH_SCHEDULE")) {
+        if (std::string(sch) == "raxml") schedule_raxml = true;
+        else if (*sch) return fail(tool, std::string("PEPRML_SEARCH_SCHEDULE: only \"raxml\" is known, got ") + sch);
     }
     if (aln_f.empty() || run.empty()) return fail(tool, "usage: raxmlHPC -f d|e|g -m PROTGAMMAWAG -s aln.phy -n run [-t tree] [-z trees]");
     // Built in: PROTGAMMAWAG, PROTGAMMAWAGF (the same exchangeabilities with frequencies counted from the alignment) and
@@ -243,6 +258,22 @@ int main(int argc, char **argv) {
             std::ofstream("RAxML_parsimonyTree." + run) << res.newick << "\n";     // topology only, read at RAxMLRunner.java:338-359
             info << "Parsimony tree length: " << mp << "\n";
             pml_result_free(&res);
+        }
+    } else if (f == "d" && (radius_i > 0 || schedule_raxml)) {
+        pml_search_opts2 o2; std::memset(&o2, 0, sizeof o2);
+        o2.base.optimize_alpha = 1; o2.base.nni = 1; o2.base.spr_radius = radius_i; o2.base.epsilon = 1e-3; o2.base.seed = seed;
+        o2.radius_mode = radius_i > 0 ? PML_RADIUS_FIXED : PML_RADIUS_AUTO;
+        // the schedule: thorough phase with the three best candidates of a prune (tools/search_schedule_eval.py)
+        if (schedule_raxml) { o2.thorough = 1; o2.thorough_top = 3; }
+        pml_result res; pml_search_trace tr;
+        rc = pml_search2(ctx, &v, nullptr, &model, &o2, &res, &tr);
+        if (!rc) {
+            const std::string nw = reformat(res.newick, 20, true);
+            std::ofstream("RAxML_result." + run) << nw << "\n"; std::ofstream("RAxML_bestTree." + run) << nw << "\n";
+            char b[320]; std::snprintf(b, sizeof b, "rearrangement radius: %d (%s)%s, %d accepted search steps\nFinal GAMMA-based Score of best tree %.6f\nalpha: %.6f\nTree-Length: %.6f\n",
+                                       tr.radius_chosen, radius_i > 0 ? "given with -i" : "determined on the start tree", schedule_raxml ? ", thorough phase on" : "", tr.nsteps, res.lnl, res.alpha, res.tree_length);
+            info << b; logf << "0.0 " << res.lnl << "\n";
+            pml_search_trace_free(&tr); pml_result_free(&res);
         }
     } else if (f == "d") {
         pml_search_opts opts = {1, 1, 5, 1e-3, seed};       // parsimony start (-p seed), NNI + lazy SPR radius 5 ("best rearrangement setting 5")

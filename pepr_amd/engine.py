@@ -12,6 +12,7 @@ KERNELS = {"pmat": 0, "newview": 1, "evaluate": 2, "sumtable": 3, "newton": 4, "
            "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9}
 PI_RAXML_3DP, PI_WAG_FULL, PI_EMPIRICAL = 0, 1, 2      # PI_EMPIRICAL = PROTGAMMAWAGF (frequencies counted per gene)
 SUPPORT_EQUAL_TAXA, SUPPORT_DECORATOR, SUPPORT_RESTRICTED = 0, 1, 2      # pml_jackknife2 / pml_support_tree_rule counting rules
+RADIUS_FIXED, RADIUS_AUTO, SPR_RADIUS_MAX = 0, 1, 25       # pml_search_opts2.radius_mode, PML_SPR_RADIUS_MAX
 PI_GTR = 3             # PROTGAMMAGTR: exchangeabilities estimated per gene by the optimising calls, empirical frequencies
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
@@ -93,6 +94,28 @@ def constraints_from_tree(newick):
     return taxa, rows
 
 
+def _edge_sets(text, n):
+    return [frozenset(b.split("\n")) for b in text.split("\n\n")] if n else []
+
+
+def spr_enumerate(newick, pruned_leaves, rmin, rmax, constraints=None):
+    """Host-only door of the SPR candidate enumeration the search uses: list of (far-side leaf set, distance) in engine order."""
+    L = _lib.load()
+    o = _opts(constraints=constraints)
+    n, dist, edges = C.c_int(0), C.c_void_p(), C.c_void_p()
+    rc = L.pml_debug_spr_enumerate(newick.encode(), "\n".join(pruned_leaves).encode(), int(rmin), int(rmax), o.nconstraints,
+                                   o.constraint_ntax, o.constraint_names, o.constraint_rows, C.byref(n), C.byref(dist), C.byref(edges))
+    if rc:
+        raise PmlError(rc, L.pml_last_error(None).decode())
+    try:
+        d = C.cast(dist, C.POINTER(C.c_int))
+        sets = _edge_sets(C.string_at(edges).decode(), n.value)
+        return [(sets[i], d[i]) for i in range(n.value)]
+    finally:
+        L.pml_free(dist)
+        L.pml_free(edges)
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -134,7 +157,7 @@ class Context:
             pass
 
     # ---- one-shot, gene-batched ----
-    def _oneshot(self, fn, genes, newicks, model, extra):
+    def _oneshot(self, fn, genes, newicks, model, extra, after=()):
         keep = []
         n = len(genes)
         alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
@@ -142,7 +165,7 @@ class Context:
         if newicks is not None:
             nw = (C.c_char_p * n)(*[(s.encode() if s is not None else None) for s in newicks])
         res = (_lib.Result * n)()
-        rc = fn(self.ptr, n, alns, nw, C.byref(model), *extra, res)
+        rc = fn(self.ptr, n, alns, nw, C.byref(model), *extra, res, *after)
         out = []
         if rc == 0:
             for r in res:
@@ -169,6 +192,61 @@ class Context:
         """seed != 0: RAxML-style randomised stepwise-addition parsimony start trees instead of NJ."""
         o = _opts(optimize_alpha, nni, spr_radius, epsilon, seed=seed, constraints=constraints)
         return self._oneshot(self.L.pml_search_batch, genes, start_newicks, _model(ncat, alpha, pi_mode), (C.byref(o),))
+
+    def search2(self, genes, start_newicks=None, alpha=1.0, ncat=4, pi_mode=PI_RAXML_3DP, optimize_alpha=True, nni=True,
+                radius="auto", radius_step=0, radius_max=0, thorough=False, thorough_top=0, thorough_radius_max=0,
+                epsilon=1e-3, constraints=None, seed=0, trace=False):
+        """RAxML's schedule (pml_search2_batch).  radius: "auto" = determined per gene on its start tree, or a fixed
+        radius 0..25 (honoured, no clamp).  Returns the result dicts; with trace=True (results, traces), a trace being
+        {"radius_chosen", "trial_radius", "trial_lnl", "lnl_start", "steps": [{"phase", "rmin", "rmax", "distance",
+        "lnl_before", "lnl_after", "newick_after"}]}."""
+        auto = radius == "auto"
+        o2 = _lib.SearchOpts2()
+        o2.base = _opts(optimize_alpha, nni, 0 if auto else int(radius), epsilon, seed=seed, constraints=constraints)
+        o2.radius_mode = RADIUS_AUTO if auto else RADIUS_FIXED
+        o2.radius_step, o2.radius_max = int(radius_step), int(radius_max)
+        o2.thorough, o2.thorough_top, o2.thorough_radius_max = int(bool(thorough)), int(thorough_top), int(thorough_radius_max)
+        n = len(genes)
+        tr = (_lib.SearchTrace * n)() if trace else None
+        try:
+            res = self._oneshot(self.L.pml_search2_batch, genes, start_newicks, _model(ncat, alpha, pi_mode), (C.byref(o2),),
+                                after=(tr,) if trace else (None,))
+            if not trace:
+                return res
+            out = []
+            for t in tr:
+                steps = []
+                for i in range(t.nsteps):
+                    s = t.steps[i]
+                    steps.append({"phase": s.phase, "rmin": s.rmin, "rmax": s.rmax, "distance": s.distance, "lnl_before": s.lnl_before,
+                                  "lnl_after": s.lnl_after, "newick_after": C.string_at(s.newick_after).decode()})
+                out.append({"radius_chosen": t.radius_chosen, "trial_radius": [t.trial_radius[i] for i in range(t.ntrials)],
+                            "trial_lnl": [t.trial_lnl[i] for i in range(t.ntrials)], "lnl_start": t.lnl_start, "steps": steps})
+            return res, out
+        finally:
+            if tr is not None:
+                for t in tr:
+                    self.L.pml_search_trace_free(C.byref(t))
+
+    def debug_spr_scores(self, gene, newick, pruned_leaves, rmin, rmax, alpha=1.0, ncat=4, pi_mode=PI_RAXML_3DP, thorough_top=0):
+        """Test door of one prune: list of (far-side leaf set, distance, lazy score, thorough) in engine order; thorough =
+        (score, pendant, near half, far half) for the thorough_top best lazy scores (< 0: all), else None."""
+        keep = []
+        aln = _aln_struct(gene[0], gene[1], keep)
+        m = _model(ncat, alpha, pi_mode)
+        n, dist, edges, lazy, th = C.c_int(0), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.pml_debug_spr_scores(self.ptr, C.byref(aln), newick.encode(), C.byref(m), "\n".join(pruned_leaves).encode(),
+                                                int(rmin), int(rmax), int(thorough_top), C.byref(n), C.byref(dist), C.byref(edges),
+                                                C.byref(lazy), C.byref(th)))
+        try:
+            d = C.cast(dist, C.POINTER(C.c_int))
+            z = C.cast(lazy, C.POINTER(C.c_double))
+            t = C.cast(th, C.POINTER(C.c_double))
+            sets = _edge_sets(C.string_at(edges).decode(), n.value)
+            return [(sets[i], d[i], z[i], None if t[4 * i] != t[4 * i] else tuple(t[4 * i + q] for q in range(4))) for i in range(n.value)]
+        finally:
+            for q in (dist, edges, lazy, th):
+                self.L.pml_free(q)
 
     def sh_support(self, genes, newicks, alpha=1.0, ncat=4, pi_mode=PI_RAXML_3DP, nboot=1000, seed=314159):
         """FastTree's SH-like local supports for given trees: list of dicts, "newick" carries 0-1 labels (3 decimals)."""

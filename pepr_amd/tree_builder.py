@@ -78,6 +78,11 @@ def _model_from_matrix(matrix, ctx=None):
                      "not a variant spelling)" % matrix)
 
 
+# candidates of a prune that get the thorough insertion under setSearchSchedule("raxml") and the shim's PEPRML_SEARCH_SCHEDULE=raxml:
+# DESIGN.md 9, the table of tools/search_schedule_eval.py
+THOROUGH_TOP = 3
+
+
 class RAxMLRunner:
     def __init__(self, threads=1, ctx=None):
         self.threads = threads
@@ -97,12 +102,25 @@ class RAxMLRunner:
         self.parsimonyWithBLTree = None
         self.bestTreeWithSupports = None
         self.seed = 12345
+        self.searchSchedule = None    # None: one fixed radius (spr_radius); "raxml": pml_search2's schedule, radius determined per gene
+        self.radiusChosen = None
 
     def setAlignment(self, a):
         self.alignment = a
 
     def getAlignment(self):
         return self.alignment
+
+    def setSearchSchedule(self, s):
+        """None (default): today's search at spr_radius.  "raxml": RAxML's schedule -- the rearrangement radius is
+        determined on the start tree (5, 10 ... 25), fast lazy SPR cycles at it, then the thorough phase with the
+        THOROUGH_TOP best candidates of a prune (engine.Context.search2)."""
+        if s not in (None, "raxml"):
+            raise ValueError("search schedule must be None or \"raxml\", got %r" % (s,))
+        self.searchSchedule = s
+
+    def getRadiusChosen(self):
+        return self.radiusChosen
 
     def setMatrix(self, m):
         self.matrix = m
@@ -166,7 +184,11 @@ class RAxMLRunner:
                 self.bestTreeWithSupports, self.lnl, self.alpha = r["newick"], r["lnl"], r["alpha"]
                 self.bestTree = None                                              # -f a writes no RAxML_result
                 return
-            r = ctx.search([gene], None, spr_radius=self.spr_radius, seed=self.seed, **mdl)[0]      # parsimony start, as -f d
+            if self.searchSchedule == "raxml":
+                res, tr = ctx.search2([gene], None, radius="auto", thorough=True, thorough_top=THOROUGH_TOP, seed=self.seed, trace=True, **mdl)
+                r, self.radiusChosen = res[0], tr[0]["radius_chosen"]
+            else:
+                r = ctx.search([gene], None, spr_radius=self.spr_radius, seed=self.seed, **mdl)[0]      # parsimony start, as -f d
             self.bestTree, self.lnl, self.alpha = r["newick"], r["lnl"], r["alpha"]
         except Exception as e:          # reference: rc logged, result stays null
             log.error("RAxMLRunner failed: %s", e)
