@@ -28,6 +28,11 @@
  *   pml_refine_next<- .../pepr/tree/PhylogeneticTreeRefiner.java:298-359 + AdvancedTree.java:1061-1098
  *   pml_support_tree<- .../pepr/tree/TreeSupportDecorator.java:86-163 addSupportValues(): integer
  *                        bipartition counts of the support trees written as node labels of the main tree
+ *   pml_nj_tree    <- .../pepr/tree/pipeline/PhylogeneticTreeBuilder.java:198-208 buildNeighborJoiningTree() (method `nj`) and
+ *                        .../pepr/tree/pipeline/PhylogenomicPipeline2.java:1279-1293 buildConcatenatedNeighborJoiningTree() (`-nj true`):
+ *                        SequenceAlignment.getPairwiseScores (BLOSUM62 as AlignmentUtilities loads it), then
+ *                        TreeBuilder.getNJTreeString / getNJTopology; pml_nj_jackknife is the gene-wise jackknife with
+ *                        `-full_tree_method nj -support_tree_method nj`
  *   pml_tree_tests <- .../pepr/tree/TreeComparison.java:812-885 runConsel(): `raxmlHPC -f g -z trees` piped through
  *                        `makermt -b 10 --puzzle`, `consel`, `catpv -v` -> the table of AU / KH / SH / bootstrap p-values;
  *                        pml_rell_tests is the makermt | consel | catpv half alone, on a per-site lnL table the caller has
@@ -510,6 +515,58 @@ int pml_debug_rell_weighted(pml_ctx *ctx, long long nsites, int ntrees, const do
  * columns and their order are catpv's documented ones, the exact spacing is this project's definition. */
 int pml_catpv_table(const pml_tree_test_result *r, const pml_tree_test_weighted *w, char **out);
 
+/* The reference's `nj` tree-building method (PhylogeneticTreeBuilder.java:198-208, PhylogenomicPipeline2.java:1279-1293), the one
+ * method whose reference is source code: parity is PINNED here -- same topology and child order in the text, every branch length
+ * the same bits as the Java's double (the spelling of the numbers is this library's: the shortest of 15, 16 or 17 significant
+ * digits that reads back to the same double, so "0" where Java prints "0.0").
+ *   codes   ARNDCQEGHILKMFPSTWYV = 0..19, B = 20, Z = 21, X = 22, '-' and '?' = 23, either letter case
+ *           (AlignmentUtilities.convertAminaAcidSequenceToInts :174-342).  The Java DROPS every other byte (J, O, U, *, '.', digits,
+ *           blanks) and shifts the rest of the row; that is not reproduced: such an alignment is refused with PML_EPARSE, and
+ *           pml_last_error names the taxon, the column (0-based) and the byte.
+ *   table   24 x 24 ints, row major, table[c_i][c_j], entries in [-128, 127] (else PML_EINVAL).  NULL = BLOSUM62 as
+ *           loadScoringMatrixFromResource (:371-398) leaves it (pml_pairscore_table_blosum62): rows and columns 0..22 are the first
+ *           23 of the file, whose order is A..V B J Z X *, so code Z reads the file's J line, code X the file's Z line, and the gap
+ *           row and column are 0.  A table need not be symmetric: every ordered pair is computed.
+ *           A taxon that a gene of a concatenation lacks is a row of '?': it scores table[gap][c] against code c, whatever the table.
+ *   scores  S[i][j] = -1 + sum_k table[c_i(k)][c_j(k)] (SequenceAlignment.getPairwiseScores :1042-1067; the -1 is its
+ *           Arrays.fill), diagonal included, computed on the device (k_pairscore); exact integers.
+ *   trees   PML_NJ_TREE = TreeBuilder.getNJTreeString (:152-344): similarities become distances max(0, max_i S[i][i]) - S (non-zero
+ *           diagonal, row sums include it), Q = (n-2) D - sum_i - sum_j, the first strict minimum over i < j in row-major order is
+ *           merged, its two lengths are clamped at 0, the merged node goes to index 0; the last three lengths are NOT clamped
+ *           (negative lengths are printed).  PML_NJ_TOPOLOGY = getNJTopology (:34-140), the `-nj true` path: the first strict
+ *           maximum of the similarities (minimum of distances) is merged, new values are plain means, "(x,y);" without lengths.
+ *           Fewer than 4 taxa: PML_EINVAL (the Java returns null for 3).
+ * The score of a concatenation is the sum of its genes' scores (a taxon a gene lacks is a row of '?': 0), so the calls that take
+ * genes compute every gene's matrix once, in one k_pairscore launch (more when the code bytes are uploaded in sub-batches by free
+ * HBM; PML_HBM_BUDGET_MB as for pml_jackknife), and build each replicate's matrix as an integer sum on the device. */
+enum { PML_NJ_DISTANCE = 0, PML_NJ_SIMILARITY = 1 };
+enum { PML_NJ_TREE = 0 /* getNJTreeString */, PML_NJ_TOPOLOGY = 1 /* getNJTopology */ };
+int pml_pairscore_table_blosum62(int table_out[576]);                                  /* host-only */
+/* host-only: the tree of an n x n matrix (row major) of the given type; *newick_out is released with pml_free */
+int pml_nj_from_matrix(int n, const char *const *names, const double *m, int matrix_type, int form, char **newick_out);
+int pml_pairwise_scores(pml_ctx *ctx, const pml_alignment *aln, const int *table576 /* NULL = BLOSUM62 as loaded */,
+                        double *scores_out /* ntax*ntax */);
+/* buildNeighborJoiningTree (form PML_NJ_TREE) / buildConcatenatedNeighborJoiningTree (PML_NJ_TOPOLOGY) of one alignment */
+int pml_nj_tree(pml_ctx *ctx, const pml_alignment *aln, const int *table576, int form, char **newick_out);
+/* nrep trees, replicate r = the concatenation (MSAConcatenator: sorted taxon union) of the genes sel[r*k .. r*k+k); sel NULL with
+ * nrep 1 = all genes.  newicks_out: nrep lines; scores_out (optional): the replicates' nu x nu score blocks one after the other;
+ * ntax_out (optional): nu per replicate.  All three are released with pml_free. */
+int pml_nj_replicates(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nrep, int k, const int *sel, const int *table576, int form,
+                      char **newicks_out, double **scores_out, int **ntax_out);
+/* The gene-wise jackknife with NJ trees throughout: the full tree (getNJTreeString on all genes) and opts->reps support trees on
+ * the subsets pml_jackknife_draw gives for (ngenes, reps, subset_size, seed), ONE k_pairscore launch for all of it; the supports
+ * are counted on the returned strings under support_rule (PML_SUPPORT_*) and written behind the ')' of the main tree's inner
+ * nodes, whose text and lengths are otherwise the NJ tree's own.  shard_world > 1 is refused (PML_EINVAL): the whole loop is
+ * cheaper than a gather.  spr_radius_full and epsilon are not used. */
+int pml_nj_jackknife(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_jackknife_opts *opts, const int *table576,
+                     int support_rule, char **main_newick_out, char **support_newicks_out);
+/* test hook of k_pairscore: the raw sums (without the -1) with chunk_sites sites per workgroup (a multiple of 16, at most 2^20;
+ * 0 = the default), so that small alignments cross chunk boundaries */
+int pml_debug_pairscores(pml_ctx *ctx, const pml_alignment *aln, const int *table576, int chunk_sites, long long *out /* ntax*ntax */);
+/* k_pairscore_sum launches on this context so far (one per pml_nj_replicates / pml_nj_jackknife call) and, with cfg.profile = 1,
+ * their summed HIP-event time; k_pairscore itself is counted by pml_kernel_stats(PML_K_PAIRSCORE).  Never reset. */
+int pml_pairscore_sum_stats(pml_ctx *ctx, long long *launches, double *total_ms);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);
@@ -533,7 +590,8 @@ enum { PML_K_PMAT = 0, PML_K_NEWVIEW = 1, PML_K_EVALUATE = 2, PML_K_SUMTABLE = 3
        PML_K_REDUCE = 5,
        PML_K_HOST_BUILD = 6 /* CPU ms building descriptors */, PML_K_HOST_WAIT = 7 /* CPU ms in stream sync */,
        PML_K_MODEL = 8 /* model builds (k_model): eigen-systems of per-gene and registered rate matrices */, 
-       PML_K_CODEHIST = 9 /* code histograms of device-gathered replicates (k_codehist); bytes = code-matrix bytes read */, PML_K_COUNT = 10 };
+       PML_K_CODEHIST = 9 /* code histograms of device-gathered replicates (k_codehist); bytes = code-matrix bytes read */,
+       PML_K_PAIRSCORE = 10 /* pair scores of the nj method (k_pairscore); bytes = code bytes read */, PML_K_COUNT = 11 };
 int pml_kernel_stats(pml_ctx *ctx, int kernel, long long *launches, double *total_ms,
                      double *algo_bytes /* algorithmic bytes moved, SURVEY 8d figures */);
 /* algorithmic flops of the launches counted by pml_kernel_stats, SURVEY 8d's per-operation figures (newview inner-inner 6480,

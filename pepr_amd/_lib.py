@@ -24,6 +24,8 @@ SYMBOLS = [
     "pml_rell_tests_weighted", "pml_tree_tests_weighted", "pml_tree_test_weighted_free", "pml_debug_rell_weighted", "pml_catpv_table",
     "pml_jackknife2", "pml_support_tree_rule", "pml_debug_replicate_freqs",
     "pml_search2", "pml_search2_batch", "pml_search_trace_free", "pml_debug_spr_enumerate", "pml_debug_spr_scores",
+    "pml_pairscore_table_blosum62", "pml_nj_from_matrix", "pml_pairwise_scores", "pml_nj_tree", "pml_nj_replicates", "pml_nj_jackknife",
+    "pml_debug_pairscores", "pml_pairscore_sum_stats",
 ]
 
 
@@ -200,5 +202,13 @@ def load():
     L.pml_debug_spr_enumerate.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, cpp, cpp, ip, C.POINTER(vp), C.POINTER(vp)]
     L.pml_debug_spr_scores.argtypes = [vp, ap, C.c_char_p, mp, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(vp), C.POINTER(vp),
                                        C.POINTER(vp), C.POINTER(vp)]
+    L.pml_pairscore_table_blosum62.argtypes = [ip]
+    L.pml_nj_from_matrix.argtypes = [C.c_int, cpp, dp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.pml_pairwise_scores.argtypes = [vp, ap, ip, dp]
+    L.pml_nj_tree.argtypes = [vp, ap, ip, C.c_int, C.POINTER(vp)]
+    L.pml_nj_replicates.argtypes = [vp, C.c_int, ap, C.c_int, C.c_int, ip, ip, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.pml_nj_jackknife.argtypes = [vp, C.c_int, ap, C.POINTER(JackknifeOpts), ip, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.pml_debug_pairscores.argtypes = [vp, ap, ip, C.c_int, lp]
+    L.pml_pairscore_sum_stats.argtypes = [vp, lp, dp]
     _lib = L
     return L

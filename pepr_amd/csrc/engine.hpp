@@ -14,7 +14,7 @@ namespace pml {
 
 constexpr int MAXTAIL = 4;            // tail requests (evaluate / sumtable+Newton) per gene per run()
 
-enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_CODEHIST = 9, K_COUNT = 10 };
+enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_CODEHIST = 9, K_PAIRSCORE = 10, K_COUNT = 11 };
 
 // Model codes (pml_model.pi_mode): 0 / 1 WAG with fixed frequencies, 2 WAG with the gene's empirical frequencies, 3 GTR
 // (exchangeabilities estimated per gene, empirical frequencies), 16 + 2 i the i-th registered matrix with its own
@@ -43,6 +43,7 @@ struct Ctx {
     bool valid_code(int pm) const { return (pm >= 0 && pm <= PM_GTR) || matrix_of(pm) != nullptr; }
     std::string model_name(int pm) const;         // the RAxML name of a code, for messages
     struct KStat { long long launches = 0; double ms = 0; double bytes = 0; double flops = 0; } stats[K_COUNT];
+    long long pairsum_launches = 0; double pairsum_ms = 0;      // k_pairscore_sum launches and (profile mode) their HIP-event time (pml_pairscore_sum_stats)
     long long newton_giveups = 0, newton_reissued = 0, newton_seq_launches = 0;   // k_newton fallback statistics (pml_newton_fallbacks)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;

@@ -185,6 +185,19 @@ void launch_gather(const GatherSeg *segs, int nsegs, int max_npat, hipStream_t s
 // that hold `code`; one launch for all replicates, `out` (nreqs x NCODES, 64-bit integers) zeroed by the caller
 struct CodeHistReq { const uint8_t *codes; const double *weight; int ntax, mpad; };
 void launch_codehist(const CodeHistReq *reqs, int nreqs, int max_mpad, long long *out, hipStream_t s);
+// pairscore.hip k_pairscore: out[i][j] += sum_k table[codes[i][k]][codes[j][k]] over the sites of the request's gene, every
+// ORDERED taxon pair (the table may be asymmetric); one launch for all requests.  codes: ntax rows of ld bytes (ld a multiple
+// of 16, the array 16-byte aligned, every byte < PS_CODES); out: ntax x ntax 64-bit integers zeroed by the caller on the
+// same stream.  table: PS_CODES x PS_TSTRIDE int8 in device memory.  chunk_sites: sites per workgroup, a multiple of 16,
+// <= PS_MAX_CHUNK (the int32 accumulator of a pair holds a whole chunk)
+constexpr int PS_CODES = 24, PS_TSTRIDE = 32, PS_TILE = 16, PS_STAGE = 512, PS_MAX_CHUNK = 1 << 20, PS_CHUNK_DEFAULT = 2048;
+struct PairScoreReq { const uint8_t *codes; long long *out; int ntax, nsites, ld; };
+void launch_pairscore(const PairScoreReq *reqs, int nreqs, int max_ntax, int max_nsites, int chunk_sites, const int8_t *table, hipStream_t s);
+// pairscore.hip k_pairscore_sum: out[i][j] = sum over the nsel selected genes g of S_g[loc_g(i)][loc_g(j)] for the nu x nu pairs
+// of a replicate's taxon union; loc (nsel rows of nu ints, -1 = the gene lacks the taxon: contributes 0) and sel index the
+// call-wide arrays S (per-gene matrices) and gene_ntax
+struct PairSumReq { const int *sel; const int *loc; long long *out; int nsel, nu; };
+void launch_pairscore_sum(const PairSumReq *reqs, int nreqs, int max_nu, const long long *const *S, const int *gene_ntax, hipStream_t s);
 
 // SH-like local support of one split (FastTree's SHSupport; Guindon et al. 2010): per-pattern lnL of the current
 // arrangement (l0) and of its two NNI alternatives (l1, l2); nboot resamples of nsites alignment columns drawn with

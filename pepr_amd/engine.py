@@ -9,11 +9,14 @@ import numpy as np
 from . import _lib
 
 KERNELS = {"pmat": 0, "newview": 1, "evaluate": 2, "sumtable": 3, "newton": 4, "reduce": 5,
-           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9}
+           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9, "pairscore": 10}
 PI_RAXML_3DP, PI_WAG_FULL, PI_EMPIRICAL = 0, 1, 2      # PI_EMPIRICAL = PROTGAMMAWAGF (frequencies counted per gene)
 SUPPORT_EQUAL_TAXA, SUPPORT_DECORATOR, SUPPORT_RESTRICTED = 0, 1, 2      # pml_jackknife2 / pml_support_tree_rule counting rules
 RADIUS_FIXED, RADIUS_AUTO, SPR_RADIUS_MAX = 0, 1, 25       # pml_search_opts2.radius_mode, PML_SPR_RADIUS_MAX
 PI_GTR = 3             # PROTGAMMAGTR: exchangeabilities estimated per gene by the optimising calls, empirical frequencies
+NJ_DISTANCE, NJ_SIMILARITY = 0, 1      # pml_nj_from_matrix matrix types (TreeBuilder.DISTANCE / SIMILARITY)
+NJ_TREE, NJ_TOPOLOGY = 0, 1            # getNJTreeString (lengths) / getNJTopology (the `-nj true` path)
+EINVAL = -1
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
 
@@ -128,6 +131,46 @@ def parse_paml(text):
     if rc:
         raise PmlError(rc, L.pml_last_error(None).decode())
     return ex, pi
+
+
+def _table_arg(table):
+    """a 24 x 24 score table (None = BLOSUM62 as the reference loads it) as the int[576] the C ABI takes"""
+    if table is None:
+        return None
+    t = np.ascontiguousarray(np.asarray(table).reshape(-1), dtype=np.int32)
+    if t.size != 576:
+        raise PmlError(EINVAL, "a score table has 24 x 24 entries")
+    return (C.c_int * 576)(*t.tolist())
+
+
+def blosum62_as_loaded():
+    """Host only: the 24 x 24 table AlignmentUtilities.loadScoringMatrixFromResource("BLOSUM62") leaves (codes ARNDCQEGHILKMFPSTWYV,
+    B, Z, X, gap): code Z holds the file's J line, code X the file's Z line, the gap row and column are 0."""
+    t = (C.c_int * 576)()
+    rc = _lib.load().pml_pairscore_table_blosum62(t)
+    if rc:
+        raise PmlError(rc)
+    return np.array(t[:], dtype=np.int64).reshape(24, 24)
+
+
+def nj_from_matrix(names, matrix, matrix_type=NJ_DISTANCE, form=NJ_TREE):
+    """Host only: TreeBuilder.getNJTreeString (form NJ_TREE) or getNJTopology (NJ_TOPOLOGY) of an n x n matrix -- the Java's
+    double operations in its order, so every length is the Java's bits.  Fewer than 4 names or a matrix that is not n x n:
+    PmlError(EINVAL)."""
+    L = _lib.load()
+    m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64))
+    n = len(names)
+    if m.ndim != 2 or m.shape != (n, n):
+        raise PmlError(EINVAL, "the matrix must be %d x %d, got shape %r" % (n, n, m.shape))
+    na = (C.c_char_p * n)(*[s.encode() for s in names])
+    out = C.c_void_p()
+    rc = L.pml_nj_from_matrix(n, na, _dp(m), int(matrix_type), int(form), C.byref(out))
+    if rc:
+        raise PmlError(rc)
+    try:
+        return C.string_at(out).decode()
+    finally:
+        L.pml_free(out)
 
 
 class Context:
@@ -351,6 +394,91 @@ class Context:
         if sup:
             self.L.pml_free(sup)
         return out
+
+    # ---- the reference's `nj` method: BLOSUM62 pair scores on the device (k_pairscore), TreeBuilder's NJ on the host ----
+    def pairwise_scores(self, gene, table=None):
+        """SequenceAlignment.getPairwiseScores: float64[ntax, ntax], S[i][j] = -1 + sum_k table[c_i(k)][c_j(k)]; table None =
+        BLOSUM62 as the reference loads it.  A byte outside the 24 codes is refused (PML_EPARSE)."""
+        keep = []
+        a = _aln_struct(gene[0], gene[1], keep)
+        out = np.zeros((a.ntax, a.ntax))
+        self._check(self.L.pml_pairwise_scores(self.ptr, C.byref(a), _table_arg(table), _dp(out)))
+        return out
+
+    def debug_pairscores(self, gene, table=None, chunk_sites=0):
+        """Test hook of k_pairscore: the raw integer sums (no -1) with chunk_sites sites per workgroup (0 = default)."""
+        keep = []
+        a = _aln_struct(gene[0], gene[1], keep)
+        out = np.zeros((a.ntax, a.ntax), dtype=np.int64)
+        self._check(self.L.pml_debug_pairscores(self.ptr, C.byref(a), _table_arg(table), int(chunk_sites),
+                                                out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
+    def nj_tree(self, gene, table=None, form=NJ_TREE):
+        """PhylogeneticTreeBuilder's `nj` method (NJ_TREE) or buildConcatenatedNeighborJoiningTree (NJ_TOPOLOGY) of one alignment."""
+        keep = []
+        a = _aln_struct(gene[0], gene[1], keep)
+        out = C.c_void_p()
+        self._check(self.L.pml_nj_tree(self.ptr, C.byref(a), _table_arg(table), int(form), C.byref(out)))
+        try:
+            return C.string_at(out).decode()
+        finally:
+            self.L.pml_free(out)
+
+    def nj_replicates(self, genes, sel=None, table=None, form=NJ_TREE, scores=False):
+        """One NJ tree per gene selection (sel: equally long lists of gene indices; None = one replicate of all genes) on the
+        concatenation's sorted taxon union; every gene is scored once.  -> list of Newick strings, or with scores=True
+        (trees, [float64[nu, nu] per replicate])."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        nrep, k, arr = 1, 0, None
+        if sel is not None:
+            nrep, k = len(sel), len(sel[0]) if len(sel) else 0
+            if any(len(s) != k for s in sel):
+                raise PmlError(EINVAL, "the selections must be equally long")
+            arr = (C.c_int * (nrep * k))(*[g for s in sel for g in s])
+        txt, sc, nt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.pml_nj_replicates(self.ptr, n, alns, nrep, k, arr, _table_arg(table), int(form), C.byref(txt),
+                                             C.byref(sc) if scores else None, C.byref(nt)))
+        try:
+            trees = C.string_at(txt).decode().splitlines()
+            if not scores:
+                return trees
+            nu = C.cast(nt, C.POINTER(C.c_int))[:nrep]
+            flat = np.frombuffer(C.string_at(sc, 8 * sum(x * x for x in nu)), dtype=np.float64)
+            mats, o = [], 0
+            for x in nu:
+                mats.append(flat[o:o + x * x].reshape(x, x).copy())
+                o += x * x
+            return trees, mats
+        finally:
+            for p in (txt, sc, nt):
+                if p:
+                    self.L.pml_free(p)
+
+    def nj_jackknife(self, genes, reps=100, subset_size=0, seed=0, table=None, support_rule=SUPPORT_DECORATOR):
+        """The gene-wise jackknife with NJ trees throughout (`-full_tree_method nj -support_tree_method nj`): the NJ tree of
+        all genes with, behind the ')' of every inner node, the number of the `reps` NJ support trees (subsets of
+        jackknife_draw(ngenes, reps, subset_size, seed)) that support it under support_rule -> {"newick", "support_trees"}."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        o = _lib.JackknifeOpts(reps, subset_size, seed, 0, 0.0, 0, 1)
+        main, sup = C.c_void_p(), C.c_void_p()
+        self._check(self.L.pml_nj_jackknife(self.ptr, n, alns, C.byref(o), _table_arg(table), int(support_rule), C.byref(main), C.byref(sup)))
+        try:
+            return {"newick": C.string_at(main).decode(), "support_trees": C.string_at(sup).decode().splitlines() if sup else []}
+        finally:
+            for p in (main, sup):
+                if p:
+                    self.L.pml_free(p)
+
+    def pairscore_sum_stats(self):
+        """k_pairscore_sum launches on this context so far and (profile mode) their summed HIP-event time in ms"""
+        n, ms = C.c_longlong(), C.c_double()
+        self._check(self.L.pml_pairscore_sum_stats(self.ptr, C.byref(n), C.byref(ms)))
+        return {"launches": n.value, "ms": ms.value}
 
     def debug_replicate_freqs(self, genes, sel=None):
         """Test hook for k_codehist: the code histogram of the device-gathered selection (None = all genes) and the empirical

@@ -8,6 +8,9 @@ read like the reference's own call sites; every `run()` goes through the C ABI
   RAxMLRunner              <- .../pepr/tree/RAxMLRunner.java:64-152,162-213,320-336
   FastTreeRunner           <- .../pepr/tree/FastTreeRunner.java:38-135,142-199,235
   TreeComparison.runConsel <- .../pepr/tree/TreeComparison.java:812-885
+  NeighborJoiningRunner    <- .../pepr/tree/pipeline/PhylogeneticTreeBuilder.java:198-208 buildNeighborJoiningTree (method "nj")
+  buildConcatenatedNeighborJoiningTree
+                           <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:1279-1293 (the `-nj true` path: topology only)
   buildConcatenatedTreeWithGeneWiseJackKnifeSupport
                            <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:994-1126,1227-1275,1587-1633
 
@@ -285,6 +288,50 @@ class FastTreeRunner:
         return self.result
 
 
+class NeighborJoiningRunner:
+    """The reference's `nj` method (PhylogeneticTreeBuilder.buildNeighborJoiningTree, :198-208): BLOSUM62 pair scores of the
+    alignment (SequenceAlignment.getPairwiseScores, on the device) and TreeBuilder.getNJTreeString on them -- the Java's
+    doubles bit for bit.  An alignment with a byte outside the 24 codes, which the Java drops, is refused: the result stays
+    None and the reason is logged, as for the other runners."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+        self.alignment = None
+        self.scoreMatrix = None           # None = BLOSUM62 as AlignmentUtilities.loadScoringMatrixFromResource leaves it
+        self.result = None
+        self.scores = None
+
+    def setAlignment(self, a):
+        self.alignment = a
+
+    def getAlignment(self):
+        return self.alignment
+
+    def setScoreMatrix(self, m):
+        """a 24 x 24 table of ints in [-128, 127] over the codes ARNDCQEGHILKMFPSTWYV, B, Z, X, gap; None = BLOSUM62 as loaded"""
+        self.scoreMatrix = m
+
+    def run(self):
+        ctx = self.ctx or default_context()
+        try:
+            self.result = ctx.nj_tree(self.alignment.as_gene(), table=self.scoreMatrix, form=engine.NJ_TREE)
+        except Exception as e:
+            log.error("NeighborJoiningRunner failed: %s", e)
+            self.result = None
+
+    def getResult(self):
+        return self.result
+
+
+def buildConcatenatedNeighborJoiningTree(genes, ctx=None):
+    """PhylogenomicPipeline2.buildConcatenatedNeighborJoiningTree (:1279-1293), the `-nj true` path: the concatenation's BLOSUM62
+    pair scores (every gene scored once on the device, summed over the sorted taxon union) and TreeBuilder.getNJTopology on
+    them -> "(x,y);" without lengths."""
+    ctx = ctx or default_context()
+    pairs = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
+    return ctx.nj_replicates(pairs, None, form=engine.NJ_TOPOLOGY)[0]
+
+
 class TreeComparison:
     """.../pepr/tree/TreeComparison.java:812-885 runConsel: `raxmlHPC -f g` on the trees, then `makermt -b 10 --puzzle`, `consel`
     and `catpv -v` on its per-site lnL -- here one engine call (pml_tree_tests, or pml_tree_tests_weighted).  weighted=True returns
@@ -396,22 +443,43 @@ class PhylogeneticTreeBuilder:
             f.run()
             self.setTreeString(f.getResult())
         else:
+            # NEIGHBOR_JOINING is built (NeighborJoiningRunner, buildConcatenatedNeighborJoiningTree, and both tree methods of
+            # buildConcatenatedTreeWithGeneWiseJackKnifeSupport), but this dispatch keeps refusing it: callers and the mirror test
+            # (tests/test_tree_builder_mirror.py::test_dispatch_and_errors_cpu) rely on the refusal, so it is not changed here
             raise ValueError("tree building method %r is outside the GPU path (ml, FastTree, parsimony, parsimony_bl)" % self.treeBuildingMethod)
 
 
 def buildConcatenatedTreeWithGeneWiseJackKnifeSupport(genes, reps=100, supportTreeMethod=FAST_TREE, mlMatrix="PROTGAMMAWAG",
-                                                      ctx=None, seed=1, support_rule=engine.SUPPORT_DECORATOR):
+                                                      ctx=None, seed=1, support_rule=engine.SUPPORT_DECORATOR, fullTreeMethod=ML):
     """PhylogenomicPipeline2.java:994-1126 as one engine call (pml_jackknife2).  genes: SequenceAlignments (or (taxa, rows)
     pairs) of the single-copy families.  mlMatrix goes to the full tree (buildConcatenatedTree, :855-858) and, when the
     support trees are ML trees too, to every gene-subset tree (GeneSubsetTreeRunnable.setMatrix, :1247, :1619-1620);
     FastTree support trees (the default method, :335-338) stay WAG with FastTree_WAG's frequencies.  The supports are what
     TreeSupportDecorator.addSupportValues counts on the returned support trees unless another rule is asked for.
-    -> the dict of Context.jackknife2: "newick" carries the supports, "support_trees" the replicate trees."""
-    if supportTreeMethod not in (ML, FAST_TREE):
-        raise ValueError("support tree method %r is outside the GPU path (ml, FastTree)" % supportTreeMethod)
+    supportTreeMethod "nj" (`-support_tree_method nj`): the full tree is built as ever, the support trees are NJ trees
+    (pml_nj_replicates) of the very gene subsets the seeded draw gives the other methods, and the supports are counted under
+    support_rule.  fullTreeMethod "nj" (`-full_tree_method nj`, with "nj" support trees): the whole loop is pml_nj_jackknife,
+    and "newick" is the NJ tree's own text with the counts behind its inner nodes; with ML or FastTree support trees it is
+    refused (that loop would search a full ML tree only to drop it).
+    -> the dict of Context.jackknife2: "newick" carries the supports, "support_trees" the replicate trees (the NJ loop
+    returns these two keys alone: an NJ tree has no likelihood)."""
+    if supportTreeMethod not in (ML, FAST_TREE, NEIGHBOR_JOINING):
+        raise ValueError("support tree method %r is outside the GPU path (ml, FastTree, nj)" % supportTreeMethod)
+    if fullTreeMethod not in (ML, NEIGHBOR_JOINING):
+        raise ValueError("full tree method %r is not built here (ml, nj)" % fullTreeMethod)
+    if fullTreeMethod == NEIGHBOR_JOINING and supportTreeMethod != NEIGHBOR_JOINING:
+        raise ValueError("an nj full tree takes nj support trees (support tree method %r would search a full ML tree to drop it)" % supportTreeMethod)
     full = _model_from_matrix(mlMatrix, ctx)                        # an unbuilt model name is refused before any device work
     support_pi = full["pi_mode"] if supportTreeMethod == ML else engine.PI_WAG_FULL
     ctx = ctx or default_context()
     pairs = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
+    if fullTreeMethod == NEIGHBOR_JOINING:
+        return ctx.nj_jackknife(pairs, reps=reps, seed=seed, support_rule=support_rule)
+    if supportTreeMethod == NEIGHBOR_JOINING:
+        r = ctx.jackknife2(pairs, reps=0, seed=seed, spr_radius_full=5, pi_mode=full["pi_mode"], ncat=full["ncat"], support_rule=support_rule)
+        sel = engine.jackknife_draw(len(pairs), reps, 0, seed)
+        r["support_trees"] = ctx.nj_replicates(pairs, sel, form=engine.NJ_TREE) if reps > 0 else []
+        r["newick"] = engine.support_tree_rule(r["newick"], r["support_trees"], support_rule)
+        return r
     return ctx.jackknife2(pairs, reps=reps, seed=seed, spr_radius_full=5, pi_mode=full["pi_mode"], ncat=full["ncat"],
                           support_pi_mode=support_pi, support_rule=support_rule)

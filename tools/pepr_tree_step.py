@@ -8,13 +8,18 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
     <run>.sup   the support trees, one Newick per line
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
+                         [--full-tree-method ml|nj] [--support-tree-method ml|FastTree|nj]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
                   PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
 --support-matrix  the same for the support trees (default: the full tree's; FastTree supports are PROTGAMMAWAG)
 --support-rule    0 = only replicates over the full taxon set count, 1 = TreeSupportDecorator.addSupportValues on the support
                   trees as written to <run>.sup, 2 = main split restricted to the replicate's taxa (include/peprml.h)
-Without these three the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
+--full-tree-method, --support-tree-method   PEPR's -full_tree_method / -support_tree_method; the value nj builds the trees by
+                  neighbor joining on BLOSUM62 pair scores, as the reference's TreeBuilder does (supports under --support-rule,
+                  default 1); nj for the full tree takes nj support trees (the default support method then); --support-matrix is
+                  refused with these two flags (ml support trees use --matrix, FastTree ones are WAG, nj has no model)
+Without these flags the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
 """
 import glob
 import os
@@ -58,7 +63,17 @@ def main(argv):
     reps = int(args.get("support_reps", 100))
     ctx = engine.Context(int(args.get("device", 0)))
     t0 = time.time()
-    if {"matrix", "support_matrix", "support_rule"} & set(args):
+    if {"full_tree_method", "support_tree_method"} & set(args):
+        from pepr_amd import tree_builder
+        if "support_matrix" in args:
+            raise SystemExit("--support-matrix does not go with --full-tree-method / --support-tree-method: ml support trees take --matrix, "
+                             "FastTree support trees are WAG, nj trees have no model")
+        full_method = args.get("full_tree_method", tree_builder.ML)
+        r = tree_builder.buildConcatenatedTreeWithGeneWiseJackKnifeSupport(
+            genes, reps=reps, supportTreeMethod=args.get("support_tree_method", tree_builder.NEIGHBOR_JOINING if full_method == tree_builder.NEIGHBOR_JOINING else tree_builder.FAST_TREE),
+            mlMatrix=args.get("matrix", "PROTGAMMAWAG"),
+            ctx=ctx, seed=int(args.get("seed", 1)), support_rule=int(args.get("support_rule", 1)), fullTreeMethod=full_method)
+    elif {"matrix", "support_matrix", "support_rule"} & set(args):
         from pepr_amd import tree_builder
         full = tree_builder._model_from_matrix(args.get("matrix"), ctx)
         sup = tree_builder._model_from_matrix(args["support_matrix"], ctx) if "support_matrix" in args else full
@@ -70,6 +85,9 @@ def main(argv):
     run = args["run_name"]
     open(run + ".nwk", "w").write(r["newick"] + "\n")
     open(run + ".sup", "w").write("\n".join(r["support_trees"]) + "\n")
+    if "lnl" not in r:                          # the NJ loop: no likelihood
+        print("%s: %d genes, neighbor joining, %d support trees, %.2f s -> %s.nwk %s.sup" % (run, len(genes), reps, dt, run, run))
+        return
     print("%s: %d genes, %d columns, lnL %.3f, alpha %.4f, %d support trees, %.2f s -> %s.nwk %s.sup" % (
         run, len(genes), r["nsites"], r["lnl"], r["alpha"], reps, dt, run, run))
 
