@@ -567,6 +567,61 @@ int pml_debug_pairscores(pml_ctx *ctx, const pml_alignment *aln, const int *tabl
  * their summed HIP-event time; k_pairscore itself is counted by pml_kernel_stats(PML_K_PAIRSCORE).  Never reset. */
 int pml_pairscore_sum_stats(pml_ctx *ctx, long long *launches, double *total_ms);
 
+/* The reference's `-congruence_filter` (HandyConstants.java:86, PhylogenomicPipeline2.java:234-247, filterForCongruence :429-511):
+ * which genes enter the concatenation, decided before any tree is built.  The taxa are the sorted union of the genes' names
+ * (n of them, at most 512; taxon i = bit i & 63 of word i >> 6 of a split's W = 1, 2, 4 or 8 64-bit words).  Bytes are compared
+ * by identity (no alphabet: 'a' and 'A' differ); only '-' and '?' are special; a taxon a gene lacks reads '?' in its columns.
+ *   splits   of a column (SequenceAlignment.getBipartitionsForAlignmentColumn :808-882): none when every byte is '-' or '?';
+ *            else, for every other distinct byte, the set of taxa that show it, normalised (Bipartition.java:41-64): complement
+ *            over ALL n taxa, the side with fewer members kept, on a tie the side that holds taxon 0.  Two classes that cover all
+ *            n taxa are one split.  A class of all taxa is the empty split.
+ *   counts   count(s) = the columns, over all genes, that have split s, for every s of at least 2 members (getBipartitionsForColumns
+ *            :697-719).  Counted per distinct split: the Java's Arrays.sort on a hash difference is a grouping device whose int
+ *            can overflow from 32 taxa upward, and then loses counts depending on the JDK's sort; below 32 taxa the two agree.
+ *   kept     (BipartitionSet.setBipartitions :84-139) with dist[c] = the number of distinct splits of count c: cutoff steps down
+ *            from the largest count while fewer than 4 n splits are included; K = every split with count >= cutoff, ties
+ *            included, so |K| has no bound.
+ *   cost     of a split b (getCost :642-652, isCompatible Bipartition.java:125-149) = the sum of count(k) over the k in K with
+ *            b & k non-empty, != b and != k.
+ *   genes    cost_sum = the sum of the costs of the gene's DISTINCT splits (trivial ones included, each once), summed in 64 bits
+ *            (the Java's int wherever that does not overflow); mean_cost = cost_sum / columns by integer division.  A gene
+ *            without columns is PML_EPARSE (the Java drops it from one of two arrays that it indexes with one counter).
+ *   select   p = trim_percent, divided by 100 when >= 1.0 (:191-195); idx = (int)(G - G p) in doubles; max_cost = the idx-th of
+ *            the ascending mean costs; gene g is kept iff g <= idx and mean_cost[g] <= max_cost (:497).  The first condition
+ *            compares the gene's POSITION in the input with a rank: that is the Java as it stands (with 20 genes and p = 0.1
+ *            gene 19 always goes).  p <= 0, NaN, or an idx outside the genes: PML_EINVAL (the Java throws).
+ * Splits are extracted, interned, counted and charged on the device (congruence.hip); K is chosen on the host.  The whole call
+ * is resident: when its records do not fit the HBM budget (0.85 of free HBM, or PML_HBM_BUDGET_MB) it is refused with PML_ENOMEM
+ * and a message that gives the size. */
+typedef struct {
+    int use_hash_mask;                /* test door: 0 = production (all ones) */
+    unsigned long long hash_mask;     /* ANDed onto every hash value before it is reduced to a slot: 0 makes every key probe from slot 0 */
+} pml_congruence_opts;
+typedef struct {
+    int ngenes, ntax, words;          /* G, n, W */
+    char **names;                     /* n sorted taxon names */
+    long long *cost_sum, *mean_cost;  /* [G] */
+    int *nsplits;                     /* [G] distinct splits of the gene, trivial ones included */
+    int cutoff;
+    long long nkept;                  /* |K| */
+    unsigned long long *kept_words;   /* [|K|][W], ascending as n-bit integers (word W-1 most significant) */
+    long long *kept_count, *kept_cost;/* [|K|]: what BipartitionSet.printBipartitionsAndCounts lists, and each kept split's own cost */
+    long long nrecords, ndistinct;    /* split records of all columns; distinct splits among them */
+} pml_congruence_result;
+int  pml_congruence_costs(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_congruence_opts *opts /* NULL = production */,
+                          pml_congruence_result *result);
+void pml_congruence_result_free(pml_congruence_result *result);
+/* host-only: the selection rule; keep_out[G] = 1 / 0; idx_out and max_cost_out are optional */
+int  pml_congruence_select(int ngenes, const long long *mean_cost, double trim_percent, int *keep_out, int *idx_out, long long *max_cost_out);
+int  pml_congruence_filter(pml_ctx *ctx, int ngenes, const pml_alignment *genes, double trim_percent, int *keep_out,
+                           pml_congruence_result *result /* may be NULL */);
+/* test hook of k_colsplits: the split records of one gene's columns over the given sorted union, as the kernel wrote them:
+ * *nrec_out records of 1 + *words_out 64-bit words, the column index then the split's words; *records_out is released with pml_free */
+int  pml_debug_column_splits(pml_ctx *ctx, const pml_alignment *gene, int nunion, const char *const *names_union, long long *nrec_out,
+                             int *words_out, unsigned long long **records_out);
+/* the kept splits that k_splitcost holds in LDS at a time (tests size a case beyond it) */
+int  pml_congruence_ktile(void);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);
@@ -591,7 +646,10 @@ enum { PML_K_PMAT = 0, PML_K_NEWVIEW = 1, PML_K_EVALUATE = 2, PML_K_SUMTABLE = 3
        PML_K_HOST_BUILD = 6 /* CPU ms building descriptors */, PML_K_HOST_WAIT = 7 /* CPU ms in stream sync */,
        PML_K_MODEL = 8 /* model builds (k_model): eigen-systems of per-gene and registered rate matrices */, 
        PML_K_CODEHIST = 9 /* code histograms of device-gathered replicates (k_codehist); bytes = code-matrix bytes read */,
-       PML_K_PAIRSCORE = 10 /* pair scores of the nj method (k_pairscore); bytes = code bytes read */, PML_K_COUNT = 11 };
+       PML_K_PAIRSCORE = 10 /* pair scores of the nj method (k_pairscore); bytes = code bytes read */,
+       PML_K_COLSPLIT = 11 /* congruence filter: k_colsplits launches (count pass and write pass); bytes = alignment bytes read */,
+       PML_K_SPLITCOST = 12 /* congruence filter: k_splitcost launches; bytes = split words read (distinct splits, and the kept set per workgroup) */,
+       PML_K_COUNT = 13 };
 int pml_kernel_stats(pml_ctx *ctx, int kernel, long long *launches, double *total_ms,
                      double *algo_bytes /* algorithmic bytes moved, SURVEY 8d figures */);
 /* algorithmic flops of the launches counted by pml_kernel_stats, SURVEY 8d's per-operation figures (newview inner-inner 6480,

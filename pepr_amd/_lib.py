@@ -26,6 +26,8 @@ SYMBOLS = [
     "pml_search2", "pml_search2_batch", "pml_search_trace_free", "pml_debug_spr_enumerate", "pml_debug_spr_scores",
     "pml_pairscore_table_blosum62", "pml_nj_from_matrix", "pml_pairwise_scores", "pml_nj_tree", "pml_nj_replicates", "pml_nj_jackknife",
     "pml_debug_pairscores", "pml_pairscore_sum_stats",
+    "pml_congruence_costs", "pml_congruence_result_free", "pml_congruence_select", "pml_congruence_filter", "pml_debug_column_splits",
+    "pml_congruence_ktile",
 ]
 
 
@@ -102,6 +104,18 @@ class TreeTestWeighted(C.Structure):
     _dp, _lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
     _fields_ = [("ntrees", C.c_int), ("wkh", _dp), ("wsh", _dp), ("wkh_count", _lp), ("wsh_count", _lp), ("sigma", _dp),
                 ("wkh_other", C.POINTER(C.c_int))]
+
+
+class CongruenceOpts(C.Structure):
+    _fields_ = [("use_hash_mask", C.c_int), ("hash_mask", C.c_ulonglong)]
+
+
+class CongruenceResult(C.Structure):
+    _lp = C.POINTER(C.c_longlong)
+    _fields_ = [("ngenes", C.c_int), ("ntax", C.c_int), ("words", C.c_int), ("names", C.POINTER(C.c_char_p)),
+                ("cost_sum", _lp), ("mean_cost", _lp), ("nsplits", C.POINTER(C.c_int)), ("cutoff", C.c_int), ("nkept", C.c_longlong),
+                ("kept_words", C.POINTER(C.c_ulonglong)), ("kept_count", _lp), ("kept_cost", _lp),
+                ("nrecords", C.c_longlong), ("ndistinct", C.c_longlong)]
 
 
 _lib = None
@@ -210,5 +224,13 @@ def load():
     L.pml_nj_jackknife.argtypes = [vp, C.c_int, ap, C.POINTER(JackknifeOpts), ip, C.c_int, C.POINTER(vp), C.POINTER(vp)]
     L.pml_debug_pairscores.argtypes = [vp, ap, ip, C.c_int, lp]
     L.pml_pairscore_sum_stats.argtypes = [vp, lp, dp]
+    crp = C.POINTER(CongruenceResult)
+    L.pml_congruence_costs.argtypes = [vp, C.c_int, ap, C.POINTER(CongruenceOpts), crp]
+    L.pml_congruence_result_free.argtypes = [crp]
+    L.pml_congruence_result_free.restype = None
+    L.pml_congruence_select.argtypes = [C.c_int, lp, C.c_double, ip, ip, lp]
+    L.pml_congruence_filter.argtypes = [vp, C.c_int, ap, C.c_double, ip, crp]
+    L.pml_debug_column_splits.argtypes = [vp, ap, C.c_int, cpp, lp, ip, C.POINTER(vp)]
+    L.pml_congruence_ktile.argtypes = []
     _lib = L
     return L

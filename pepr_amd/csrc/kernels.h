@@ -199,6 +199,34 @@ void launch_pairscore(const PairScoreReq *reqs, int nreqs, int max_ntax, int max
 struct PairSumReq { const int *sel; const int *loc; long long *out; int nsel, nu; };
 void launch_pairscore_sum(const PairSumReq *reqs, int nreqs, int max_nu, const long long *const *S, const int *gene_ntax, hipStream_t s);
 
+// The congruence filter (congruence.hip): the splits of every alignment column as records of W 64-bit words over the n taxa of
+// the concatenation (taxon i = bit i & 63 of word i >> 6; W = 1, 2, 4 or 8, the smallest that holds n <= CG_MAX_TAXA bits).
+// A gene's rows are raw bytes, ld bytes apart (a multiple of 16, the array 16-byte aligned), in ASCENDING order of their union
+// index; map[r] = union index of row r.  A taxon the gene lacks has no row and sets no bit.
+constexpr int CG_MAX_TAXA = 512, CG_COLS = 64 /* columns per k_colsplits workgroup */, CG_KTILE = 256 /* kept splits per LDS tile of k_splitcost */;
+constexpr int cg_words(int n) { return n <= 64 ? 1 : n <= 128 ? 2 : n <= 256 ? 4 : 8; }
+struct CgGene { const uint8_t *bytes; const uint16_t *map; int ntax, ncols, ld; long long col_base; /* index of its first column in the call */ };
+// one workgroup per entry of tile_gene (gene index; a gene's tiles are consecutive, tile_first[gene] = its first); max_ntax sizes the LDS.
+// count pass (rec == nullptr): nsplit[column] = the column's number of splits.  write pass: rec_off[column] = exclusive
+// prefix of nsplit; record rec_off[column] + i = the column's i-th split in ascending order of the class's byte, normalised;
+// rec_gene / rec_col = its gene and its column index in the call
+void launch_colsplits(const CgGene *genes, const int *tile_gene, const int *tile_first, int ntiles, int max_ntax, int n, int *nsplit,
+                      const long long *rec_off, unsigned long long *rec, int *rec_gene, long long *rec_col, hipStream_t s);
+// interning: slot[cap] (cap a power of two, filled with -1 by the caller) holds the index of the first record of its key;
+// split_id[r] = that owner's index; count[owner] += 1 for every record of at least 2 members (zeroed by the caller).
+// hash_mask is ANDed onto the hash before it is reduced to a slot.  *err is set when a probe runs through the whole table
+void launch_split_intern(const unsigned long long *rec, long long nrec, int W, int *slot, unsigned long long cap, unsigned long long hash_mask,
+                         int *split_id, int *count, int *err, hipStream_t s);
+// out[j][W] = rec[idx[j]][W]
+void launch_split_gather(const unsigned long long *rec, const int *idx, long long nidx, int W, unsigned long long *out, hipStream_t s);
+// cost_d[d] = cost_rec[dist[d]] = sum of kcount[j] over the kept splits kwords[j] that conflict with record dist[d]
+void launch_splitcost(const unsigned long long *rec, const int *dist, long long ndist, int W, const unsigned long long *kwords, const int *kcount,
+                      long long nkept, long long *cost_d, long long *cost_rec, hipStream_t s);
+// per gene: the distinct split ids of its records (second table: keys[cap] filled with ~0 by the caller), cost_sum[gene] +=
+// cost_rec[id] and ndistinct[gene] += 1 once per distinct (gene, id)
+void launch_genecost(const int *rec_gene, const int *split_id, long long nrec, const long long *cost_rec, unsigned long long *keys,
+                     unsigned long long cap, unsigned long long hash_mask, long long *cost_sum, int *ndistinct, int *err, hipStream_t s);
+
 // SH-like local support of one split (FastTree's SHSupport; Guindon et al. 2010): per-pattern lnL of the current
 // arrangement (l0) and of its two NNI alternatives (l1, l2); nboot resamples of nsites alignment columns drawn with
 // the counter hash col(r, j) = mix64((seed+1)*0x9E3779B97F4A7C15 + r*nsites + j) % nsites; a resample supports the

@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 
 KERNELS = {"pmat": 0, "newview": 1, "evaluate": 2, "sumtable": 3, "newton": 4, "reduce": 5,
-           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9, "pairscore": 10}
+           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9, "pairscore": 10, "colsplit": 11, "splitcost": 12}
 PI_RAXML_3DP, PI_WAG_FULL, PI_EMPIRICAL = 0, 1, 2      # PI_EMPIRICAL = PROTGAMMAWAGF (frequencies counted per gene)
 SUPPORT_EQUAL_TAXA, SUPPORT_DECORATOR, SUPPORT_RESTRICTED = 0, 1, 2      # pml_jackknife2 / pml_support_tree_rule counting rules
 RADIUS_FIXED, RADIUS_AUTO, SPR_RADIUS_MAX = 0, 1, 25       # pml_search_opts2.radius_mode, PML_SPR_RADIUS_MAX
@@ -474,6 +474,68 @@ class Context:
                 if p:
                     self.L.pml_free(p)
 
+    # ---- the reference's `-congruence_filter`: column splits, their counts and the genes' conflict costs on the device ----
+    def _congruence_result(self, res):
+        n, w, g, k = res.ntax, res.words, res.ngenes, res.nkept
+        names = [res.names[i].decode() for i in range(n)]
+        kept = []
+        for j in range(k):
+            bits = 0
+            for x in range(w):
+                bits |= res.kept_words[j * w + x] << (64 * x)
+            kept.append((frozenset(names[i] for i in range(n) if bits >> i & 1), res.kept_count[j], res.kept_cost[j]))
+        return {"names": names, "n": n, "cutoff": res.cutoff, "kept_splits": kept,
+                "kept_words": np.array(res.kept_words[:k * w], dtype=np.uint64).reshape(k, w),
+                "cost_sum": list(res.cost_sum[:g]), "mean_cost": list(res.mean_cost[:g]), "nsplits": list(res.nsplits[:g]),
+                "nrecords": res.nrecords, "ndistinct": res.ndistinct}
+
+    def congruence_costs(self, genes, hash_mask=None):
+        """Rules 1 to 6 of the congruence filter (include/peprml.h): per gene cost_sum, mean_cost and the number of distinct
+        splits; n, the sorted names, the cutoff and the kept splits as (set of names, count, cost), ascending as n-bit integers.
+        hash_mask is a test door: it is ANDed onto every hash value (0: every key probes from slot 0)."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        o = None if hash_mask is None else C.byref(_lib.CongruenceOpts(1, int(hash_mask)))
+        res = _lib.CongruenceResult()
+        self._check(self.L.pml_congruence_costs(self.ptr, n, alns, o, C.byref(res)))
+        try:
+            return self._congruence_result(res)
+        finally:
+            self.L.pml_congruence_result_free(C.byref(res))
+
+    def congruence_filter(self, genes, trim_percent=0.1):
+        """PhylogenomicPipeline2.filterForCongruence: congruence_costs plus the selection -> {"keep": [bool per gene], "idx",
+        "max_cost", "mean_cost", "cost_sum", "cutoff", "kept_splits", ...}"""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        res = _lib.CongruenceResult()
+        flags = (C.c_int * n)()
+        self._check(self.L.pml_congruence_filter(self.ptr, n, alns, float(trim_percent), flags, C.byref(res)))
+        try:
+            out = self._congruence_result(res)
+        finally:
+            self.L.pml_congruence_result_free(C.byref(res))
+        out.update(congruence_select(out["mean_cost"], trim_percent))          # idx and max_cost
+        out["keep"] = [bool(f) for f in flags]
+        return out
+
+    def debug_column_splits(self, gene, names_union):
+        """Test hook of k_colsplits: the split records of one gene's columns over the sorted union as the kernel wrote them ->
+        list of (column, split as an int with taxon i = bit i), in record order"""
+        keep = []
+        a = _aln_struct(gene[0], gene[1], keep)
+        nu = len(names_union)
+        na = (C.c_char_p * nu)(*[s.encode() for s in names_union])
+        nrec, w, out = C.c_longlong(), C.c_int(), C.c_void_p()
+        self._check(self.L.pml_debug_column_splits(self.ptr, C.byref(a), nu, na, C.byref(nrec), C.byref(w), C.byref(out)))
+        try:
+            flat = np.frombuffer(C.string_at(out, 8 * nrec.value * (w.value + 1)), dtype=np.uint64).reshape(nrec.value, w.value + 1)
+            return [(int(r[0]), sum(int(r[1 + x]) << (64 * x) for x in range(w.value))) for r in flat]
+        finally:
+            self.L.pml_free(out)
+
     def pairscore_sum_stats(self):
         """k_pairscore_sum launches on this context so far and (profile mode) their summed HIP-event time in ms"""
         n, ms = C.c_longlong(), C.c_double()
@@ -928,6 +990,25 @@ def jackknife_draw(ngenes, reps, subset_size=0, seed=0):
         raise PmlError(rc)
     assert rc == k
     return [list(out[r * k:(r + 1) * k]) for r in range(reps)]
+
+
+def congruence_select(mean_costs, trim_percent=0.1):
+    """Host only: filterForCongruence's selection on the genes' mean costs -> {"keep", "idx", "max_cost"}; a trim_percent of 1.0
+    or more is divided by 100; gene g is kept iff g <= idx and its mean cost <= max_cost (the Java's rule, position against rank).
+    trim_percent <= 0, NaN or an index outside the genes: PmlError(EINVAL)."""
+    L = _lib.load()
+    n = len(mean_costs)
+    m = (C.c_longlong * n)(*[int(x) for x in mean_costs])
+    keep, idx, mx = (C.c_int * n)(), C.c_int(), C.c_longlong()
+    rc = L.pml_congruence_select(n, m, float(trim_percent), keep, C.byref(idx), C.byref(mx))
+    if rc:
+        raise PmlError(rc, "trim_percent %r with %d genes" % (trim_percent, n))
+    return {"keep": [bool(k) for k in keep], "idx": idx.value, "max_cost": mx.value}
+
+
+def congruence_ktile():
+    """the kept splits k_splitcost holds in LDS at a time"""
+    return _lib.load().pml_congruence_ktile()
 
 
 def concatenate(genes, sel=None):

@@ -332,6 +332,15 @@ def buildConcatenatedNeighborJoiningTree(genes, ctx=None):
     return ctx.nj_replicates(pairs, None, form=engine.NJ_TOPOLOGY)[0]
 
 
+def filterForCongruence(genes, percentileToRemove=0.1, ctx=None):
+    """PhylogenomicPipeline2.filterForCongruence (:429-511), the `-congruence_filter` step: the genes that stay in the
+    concatenation, in input order.  Nothing is printed; Context.congruence_filter returns the costs behind the choice."""
+    ctx = ctx or default_context()
+    pairs = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
+    keep = ctx.congruence_filter(pairs, percentileToRemove)["keep"]
+    return [g for g, k in zip(genes, keep) if k]
+
+
 class TreeComparison:
     """.../pepr/tree/TreeComparison.java:812-885 runConsel: `raxmlHPC -f g` on the trees, then `makermt -b 10 --puzzle`, `consel`
     and `catpv -v` on its per-site lnL -- here one engine call (pml_tree_tests, or pml_tree_tests_weighted).  weighted=True returns

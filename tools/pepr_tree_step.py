@@ -9,6 +9,7 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
                          [--full-tree-method ml|nj] [--support-tree-method ml|FastTree|nj]
+                         [-congruence_filter] [-trim_percent 0.1]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
                   PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
@@ -19,6 +20,10 @@ usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-se
                   neighbor joining on BLOSUM62 pair scores, as the reference's TreeBuilder does (supports under --support-rule,
                   default 1); nj for the full tree takes nj support trees (the default support method then); --support-matrix is
                   refused with these two flags (ml support trees use --matrix, FastTree ones are WAG, nj has no model)
+-congruence_filter, -trim_percent P   PEPR's flags of the same names (HandyConstants.java:86, :92): before any tree is built the
+                  genes are filtered as PhylogenomicPipeline2.filterForCongruence filters them (column bipartition costs, the
+                  genes of the highest mean cost go; P of 1.0 or more is a percentage).  Prints the reference's two messages and
+                  writes <run>.congruence.tsv: file, columns, cost_sum, mean_cost, kept -- one row per gene
 Without these flags the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
 """
 import glob
@@ -58,10 +63,22 @@ def main(argv):
     if "run_name" not in args or "alignment_dir" not in args:
         raise SystemExit(__doc__)
     files = sorted(glob.glob(os.path.join(args["alignment_dir"], "*")))
-    genes = [read_fasta(f) for f in files if os.path.isfile(f)]
+    files = [f for f in files if os.path.isfile(f)]
+    genes = [read_fasta(f) for f in files]
+    files = [f for f, g in zip(files, genes) if len(g[0]) >= 3]
     genes = [g for g in genes if len(g[0]) >= 3]
     reps = int(args.get("support_reps", 100))
     ctx = engine.Context(int(args.get("device", 0)))
+    if args.get("congruence_filter", "false").lower() == "true":
+        r = ctx.congruence_filter(genes, float(args.get("trim_percent", 0.1)))
+        with open(args["run_name"] + ".congruence.tsv", "w") as f:
+            f.write("file\tcolumns\tcost_sum\tmean_cost\tkept\n")
+            for name, g, cs, mc, k in zip(files, genes, r["cost_sum"], r["mean_cost"], r["keep"]):
+                f.write("%s\t%d\t%d\t%d\t%d\n" % (os.path.basename(name), len(g[1][0]), cs, mc, int(k)))
+                if not k:
+                    print("discarding set %s cost: %d" % (os.path.basename(name), mc))
+        genes = [g for g, k in zip(genes, r["keep"]) if k]
+        print("Discarded: %d\tKept: %d" % (len(files) - len(genes), len(genes)))
     t0 = time.time()
     if {"full_tree_method", "support_tree_method"} & set(args):
         from pepr_amd import tree_builder
