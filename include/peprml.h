@@ -17,6 +17,7 @@
  *   pml_jackknife  <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:994-1126
  *                        buildConcatenatedTreeWithGeneWiseJackKnifeSupport(): full tree + N support trees on
  *                        random gene subsets (:959-977, 1227-1275, 1587-1633) + support counts, ONE call
+ *   pml_jackknife3 <- the same loop with `-full_tree_method` / `-support_tree_method` parsimony (:856-863, :1246, :1619)
  *   pml_parsimony  <- .../pepr/tree/RAxMLRunner.java:215-251  runRaxmlParsimonyWithBranchLengths():
  *                        `raxmlHPC -f d -y` -> RAxML_parsimonyTree.<run> (topology only); the caller then
  *                        runs pml_optimize on it, as the reference runs `-f e -t` (:253-272)
@@ -333,6 +334,48 @@ typedef struct {
 } pml_jackknife_opts2;
 int pml_jackknife2(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *full_model,
                    const pml_jackknife_opts2 *opts, pml_result *main_out, char **support_newicks_out);
+/* The same loop with PEPR's tree-building methods for both kinds of tree (`-full_tree_method`, `-support_tree_method`;
+ * PhylogenomicPipeline2.java:856-863, :1246, :1619; PhylogeneticTreeBuilder.java:104-115,136-161): maximum-parsimony trees
+ * (`raxmlHPC -y`) are built from the genes resident in HBM -- k_fitch_tips writes every replicate's Fitch tip vectors straight
+ * from the genes' code matrices, no concatenated text and no replicate code matrix -- and searched in lock step by pml_parsimony's
+ * stepwise addition + SPR.
+ *   support_method  PML_TREE_ML: as pml_jackknife2.  PML_TREE_PARSIMONY: every support tree is the parsimony tree of its
+ *             replicate over the replicate's sorted taxon union, returned topology only (what pml_parsimony prints);
+ *             base2.support_model is not used; the supports are counted under base2.support_rule as ever.  The replicates go
+ *             through in sub-batches sized by their Fitch pools against the HBM budget of the ML replicates; the results do
+ *             not depend on the split.  PML_TREE_PARSIMONY_BL is refused (PML_EINVAL): nothing reads a support tree's lengths.
+ *   full_method     PML_TREE_ML: as pml_jackknife2.  PML_TREE_PARSIMONY: the parsimony tree of all genes; main_out->newick is
+ *             topology only with the counts as inner labels `)87`; lnl, alpha and tree_length are 0, npatterns and nsites those
+ *             of the concatenation.  PML_TREE_PARSIMONY_BL (`-y`, then `-f e -t`): the same topology, then branch lengths and
+ *             alpha optimised under full_model from lengths 0.1 as pml_optimize does, to base.epsilon (0 = 1e-3); newick, lnl,
+ *             alpha and tree_length come from that pass; per-gene model codes work as for any replicate.
+ *   seeds     of the stepwise addition, independent of sharding and sub-batching: the full tree (unsigned)base.seed, replicate r
+ *             (its index in pml_jackknife_draw's list) (unsigned)(base.seed + 1 + r); a value of 0 would mean "input order" and
+ *             is replaced by 0x9E3779B9.
+ *   limits    a replicate whose taxon union has fewer than 3 taxa fails the call (PML_EPARSE, "replicate r: parsimony needs at
+ *             least 3 taxa").  Method values outside the lists above are PML_EINVAL, refused before anything is uploaded.
+ * opts NULL = pml_jackknife2 with opts NULL.  With both methods PML_TREE_ML the call returns pml_jackknife2's strings and numbers. */
+enum { PML_TREE_ML = 0, PML_TREE_PARSIMONY = 1, PML_TREE_PARSIMONY_BL = 2 };
+typedef struct {
+    pml_jackknife_opts2 base2;
+    int full_method;        /* PML_TREE_*: how the full tree is built */
+    int support_method;     /* PML_TREE_ML or PML_TREE_PARSIMONY */
+    int parsimony_radius;   /* pml_parsimony_opts.spr_radius of every parsimony tree of the call (RAxML: 20; 0 = stepwise addition only) */
+    int pad;
+} pml_jackknife_opts3;
+int pml_jackknife3(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *full_model,
+                   const pml_jackknife_opts3 *opts, pml_result *main_out, char **support_newicks_out,
+                   long long *mp_lengths_out /* optional, 1 + reps: [0] full tree, [1 + r] replicate r by its index in the draw;
+                                                -1 = not a parsimony tree, or not built on this rank */);
+/* k_fitch_tips launches (one per sub-batch of parsimony replicates, one per parsimony full tree, one per pml_debug_fitch_tips) and
+ * k_fitch launches (every device step of every parsimony tree, pml_parsimony* included) on this context so far.  Never reset. */
+int pml_fitch_stats(pml_ctx *ctx, long long *tips_launches, long long *fitch_launches);
+/* test door of k_fitch_tips, the counterpart of pml_debug_gather: encodes the genes into HBM, fills the Fitch tip vectors of the
+ * selection `sel` (NULL = all) exactly as pml_jackknife3 does for a replicate and reads them back: masks_out[ntax x mpad] (bit s =
+ * amino acid s possible; B = N|D, Z = Q|E, gap / unknown / absent taxon / padding = 0xFFFFF), weights_out[mpad] (0 = padding),
+ * names_out = the sorted taxon union, one per line.  The three buffers are released with pml_free. */
+int pml_debug_fitch_tips(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nsel, const int *sel, int *ntax_out,
+                         int *npat_out, int *mpad_out, unsigned **masks_out, int **weights_out, char **names_out);
 /* host-only: pml_support_tree under one of the PML_SUPPORT_* rules; support trees may cover other taxon sets than the main
  * tree's (rule 0 counts such a tree as not supporting, where pml_support_tree returns PML_EPARSE) */
 int pml_support_tree_rule(const char *main_newick, int ntrees, const char *const *support_newicks, int rule, int digits,

@@ -28,6 +28,7 @@ SYMBOLS = [
     "pml_debug_pairscores", "pml_pairscore_sum_stats",
     "pml_congruence_costs", "pml_congruence_result_free", "pml_congruence_select", "pml_congruence_filter", "pml_debug_column_splits",
     "pml_congruence_ktile",
+    "pml_jackknife3", "pml_fitch_stats", "pml_debug_fitch_tips",
 ]
 
 
@@ -75,6 +76,11 @@ class JackknifeOpts(C.Structure):
 
 class JackknifeOpts2(C.Structure):
     _fields_ = [("base", JackknifeOpts), ("support_model", C.POINTER(Model)), ("support_rule", C.c_int)]
+
+
+class JackknifeOpts3(C.Structure):
+    _fields_ = [("base2", JackknifeOpts2), ("full_method", C.c_int), ("support_method", C.c_int), ("parsimony_radius", C.c_int),
+                ("pad", C.c_int)]
 
 
 class ParsimonyOpts(C.Structure):
@@ -232,5 +238,8 @@ def load():
     L.pml_congruence_filter.argtypes = [vp, C.c_int, ap, C.c_double, ip, crp]
     L.pml_debug_column_splits.argtypes = [vp, ap, C.c_int, cpp, lp, ip, C.POINTER(vp)]
     L.pml_congruence_ktile.argtypes = []
+    L.pml_jackknife3.argtypes = [vp, C.c_int, ap, mp, C.POINTER(JackknifeOpts3), rp, C.POINTER(vp), lp]
+    L.pml_fitch_stats.argtypes = [vp, lp, lp]
+    L.pml_debug_fitch_tips.argtypes = [vp, C.c_int, ap, C.c_int, ip, ip, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     _lib = L
     return L

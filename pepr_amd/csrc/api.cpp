@@ -341,6 +341,7 @@ static int oneshot_chunk(pml_ctx *ctx, int op, int n, const pml_alignment *alns,
         }
         ctx->c.newton_giveups += w.newton_giveups; ctx->c.newton_reissued += w.newton_reissued; ctx->c.newton_seq_launches += w.newton_seq_launches;
         w.newton_giveups = w.newton_reissued = w.newton_seq_launches = 0;
+        ctx->c.fitch_launches += w.fitch_launches; w.fitch_launches = 0;           // parsimony starts of the group's genes
     }
     return rc;
 }
@@ -961,6 +962,13 @@ int pml_newton_fallbacks(pml_ctx *ctx, long long *giveups, long long *reissued, 
     if (giveups) *giveups = ctx->c.newton_giveups;
     if (reissued) *reissued = ctx->c.newton_reissued;
     if (seq_launches) *seq_launches = ctx->c.newton_seq_launches;
+    return PML_OK;
+}
+int pml_fitch_stats(pml_ctx *ctx, long long *tips_launches, long long *fitch_launches) {
+    if (!ctx) return PML_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    if (tips_launches) *tips_launches = ctx->c.fitch_tips_launches;
+    if (fitch_launches) *fitch_launches = ctx->c.fitch_launches;
     return PML_OK;
 }
 int pml_kernel_flops(pml_ctx *ctx, int k, double *flops) {

@@ -45,6 +45,7 @@ struct Ctx {
     struct KStat { long long launches = 0; double ms = 0; double bytes = 0; double flops = 0; } stats[K_COUNT];
     long long pairsum_launches = 0; double pairsum_ms = 0;      // k_pairscore_sum launches and (profile mode) their HIP-event time (pml_pairscore_sum_stats)
     long long newton_giveups = 0, newton_reissued = 0, newton_seq_launches = 0;   // k_newton fallback statistics (pml_newton_fallbacks)
+    long long fitch_tips_launches = 0, fitch_launches = 0;      // k_fitch_tips and k_fitch launches (pml_fitch_stats)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;
     std::vector<hipEvent_t> pool;
@@ -331,5 +332,12 @@ struct Batch {
 // parsimony.hip: Fitch parsimony trees (stepwise addition + SPR) for n genes, one launch per device step
 int parsimony_batch(Ctx *ctx, int n, const pml_alignment_view *alns, unsigned seed, int radius, std::vector<Tree> &trees_out,
                     std::vector<EncodedAlignment> &alns_out, std::vector<long long> &lengths_out, std::vector<int> &moves_out);
+// the same trees for gene selections over a resident store (the jackknife): tip vectors straight from the genes' code matrices
+// (k_fitch_tips, one launch for all selections), a seed per selection; names_out[r] = the selection's sorted taxon union
+int parsimony_replicates(Ctx *ctx, const GeneStore &store, const std::vector<std::vector<int>> &selections, const std::vector<unsigned> &seeds,
+                         int radius, std::vector<Tree> &trees_out, std::vector<std::vector<std::string>> &names_out, std::vector<long long> &lengths_out);
+// test door: the tip rows [ntax x mpad] and weights [mpad] k_fitch_tips writes for one selection
+int fitch_tips_readback(Ctx *ctx, const GeneStore &store, const std::vector<int> &sel, int *npat_out, int *mpad_out, std::vector<unsigned> &masks_out,
+                        std::vector<int> &weights_out, std::vector<std::string> &names_out);
 
 }  // namespace pml

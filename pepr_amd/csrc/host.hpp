@@ -52,7 +52,7 @@ struct Tree {
     static bool parse_free(const char *newick, std::vector<std::string> &names, Tree &out, std::string &err);
     std::string newick(const std::vector<std::string> &names, int digits) const;
     // labels[v] (v >= ntax) is printed after the ')' of inner node v when >= 0 (support values);
-    // the label belongs to the branch between v and its parent in the printed orientation
+    // the label belongs to the branch between v and its parent in the printed orientation; digits < 0: no lengths, `)87`
     std::string newick_labeled(const std::vector<std::string> &names, int digits, const std::vector<std::vector<int>> &edge_label) const;
     // same with real-valued labels printed with label_digits decimals (FastTree's 0-1 supports); < 0 = no label
     std::string newick_labeled(const std::vector<std::string> &names, int digits, const std::vector<std::vector<double>> &edge_label, int label_digits) const;

@@ -6,6 +6,8 @@
 // the device (GeneStore / Batch::create_replicates) and the replicates are searched as ONE batch; the support counting is TreeSupportDecorator.addSupportValues (:86-163).
 // pml_jackknife2 is the same loop under any model code (a model per replicate, its frequencies counted on the device by
 // k_codehist), with another model for the support trees and the counting rules of host.hpp support_counts_rule.
+// pml_jackknife3 adds PEPR's tree-building methods (-full_tree_method / -support_tree_method parsimony, parsimony_bl): parsimony
+// trees of the resident genes, their Fitch tips written by k_fitch_tips (parsimony.hip) -- no CLV arena, no replicate code matrix.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -120,13 +122,23 @@ extern "C" int pml_debug_gather(pml_ctx *ctx, int ngenes, const pml_alignment *g
     return PML_OK;
 }
 
-// The loop itself, for pml_jackknife (one shared-model code, SUPPORT_EQUAL_TAXA) and pml_jackknife2 (any valid code for the
-// full tree and for the support trees, any counting rule).  The caller holds the context's mutex and has checked the codes.
+// the stepwise-addition seeds of pml_jackknife3's parsimony trees (peprml.h): idx 0 = the full tree, 1 + r = replicate r of the
+// draw; 0 means "input order" to the core and is replaced
+static unsigned parsimony_seed(unsigned long long seed, int idx) {
+    const unsigned s = (unsigned)(seed + (unsigned long long)idx);
+    return s ? s : 0x9E3779B9u;
+}
+
+// The loop itself, for pml_jackknife (one shared-model code, SUPPORT_EQUAL_TAXA), pml_jackknife2 (any valid code for the
+// full tree and for the support trees, any counting rule) and pml_jackknife3 (a tree-building method for either kind of tree).
+// The caller holds the context's mutex and has checked the codes and the methods.  mp_out (optional, 1 + reps): Fitch lengths.
 static int jackknife_run(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *model, const pml_model *support_model,
-                         int rule, const pml_jackknife_opts *opts, pml_result *main_out, char **support_out) {
+                         int rule, const pml_jackknife_opts *opts, pml_result *main_out, char **support_out,
+                         int full_method = PML_TREE_ML, int support_method = PML_TREE_ML, int pars_radius = 20, long long *mp_out = nullptr) {
     pml_fpguard fpg;
     std::memset(main_out, 0, sizeof *main_out);
     if (support_out) *support_out = nullptr;
+    if (mp_out) for (int i = 0; i <= (opts ? std::max(opts->reps, 0) : 100); ++i) mp_out[i] = -1;
     const int reps = opts ? opts->reps : 100;
     int subset = (opts && opts->subset_size > 0) ? opts->subset_size : ngenes / 2;
     subset = std::max(1, std::min(subset, ngenes));
@@ -158,9 +170,38 @@ static int jackknife_run(pml_ctx *ctx, int ngenes, const pml_alignment *genes, c
         // the support trees' model (FastTree supports stay WAG while the full tree uses mlMatrix, PhylogenomicPipeline2.java:335-338)
         const int sncat = support_model ? support_model->ncat : 4, spm = support_model ? support_model->pi_mode : 0;
         const double salpha = support_model ? support_model->alpha : 1.0;
+        const unsigned long long seed = opts ? opts->seed : 0;
+        auto draw_index = [&](int r) { return srank + r * sworld; };          // this rank's replicate r in the draw's list
+        if (support_method == PML_TREE_PARSIMONY) {          // refused before any tree is built, under the replicate's index in the draw
+            for (int r = 0; r < reps_here; ++r) {
+                std::set<std::string> taxa;
+                for (int g : rep[r]) taxa.insert(store.items[g].aln.names.begin(), store.items[g].aln.names.end());
+                if (taxa.size() < 3) return ctx->c.fail(PML_EPARSE, "replicate " + std::to_string(draw_index(r)) + ": parsimony needs at least 3 taxa");
+            }
+        }
         // full tree
-        Tree main_tree; std::vector<std::string> main_names; double main_lnl = 0, main_alpha = alpha; int main_npat = 0, main_nsites = 0;
-        if (srank == 0) {
+        Tree main_tree; std::vector<std::string> main_names; double main_lnl = 0, main_alpha = full_method == PML_TREE_PARSIMONY ? 0.0 : alpha; int main_npat = 0, main_nsites = 0;
+        if (srank == 0 && full_method != PML_TREE_ML) {
+            // the parsimony tree of all genes, its tips written from the resident genes (k_fitch_tips)
+            std::vector<Tree> pt; std::vector<std::vector<std::string>> pn; std::vector<long long> pl;
+            if (int rc = parsimony_replicates(&ctx->c, store, {all}, {parsimony_seed(seed, 0)}, pars_radius, pt, pn, pl)) return rc;
+            main_tree = pt[0]; main_names = pn[0];
+            for (auto &it : store.items) { main_npat += it.aln.npat; main_nsites += it.aln.nsites; }
+            if (mp_out) mp_out[0] = pl[0];
+            if (full_method == PML_TREE_PARSIMONY_BL) {
+                // `-f e -t` on that topology: lengths from 0.1 and alpha, as pml_optimize runs them
+                Batch b;
+                struct DropB { Batch &b; ~DropB() { b.destroy(); } } dropb{b};
+                if (int rc = b.create_replicates(&ctx->c, store, {all}, pm, ncat, alpha)) return rc;
+                Gene &G = b.genes[0];
+                std::string err;
+                if (G.aln.names != main_names || !Tree::parse(main_tree.newick(main_names, 6).c_str(), G.aln.names, G.tree, err))
+                    return ctx->c.fail(PML_EINVAL, "parsimony tree does not fit the replicate of all genes: " + err);
+                b.invalidate_all(0); G.mark_all(); ++b.topo_epoch;
+                if (int rc = b.optimize(true, eps, &main_lnl)) return rc;
+                main_tree = G.tree; main_alpha = G.alpha; main_npat = G.aln.npat; main_nsites = G.aln.nsites;
+            }
+        } else if (srank == 0) {
             Batch b; int rc = b.create_replicates(&ctx->c, store, {all}, pm, ncat, alpha);
             if (!rc) rc = b.search(true, spr_full, true, eps, &main_lnl);
             if (rc) { b.destroy(); return rc; }
@@ -182,7 +223,37 @@ static int jackknife_run(pml_ctx *ctx, int ngenes, const pml_alignment *genes, c
                 const size_t mp = (pats + 31) / 32 * 32, nt = std::max<size_t>(taxa.size(), 3), slots = 3 * (nt - 2) + NSCRATCH + MAXTAIL;
                 return slots * CLV_ROWS * ((mp + 127) / 128 * 128) * 8 + slots * mp * 4 + nt * mp + 64 * mp + (1 << 16);
             };
-            for (int begin = 0; begin < reps_here;) {
+            // a parsimony replicate holds its Fitch pool alone: tips, 3 messages per inner node and radius + 2 path vectors for
+            // each of at most 64 prune groups, 4 B per pattern each -- no CLV arena
+            auto pars_bytes = [&](const std::vector<int> &sel) {
+                size_t pats = 0; std::set<std::string> taxa;
+                for (int g : sel) { pats += (size_t)store.items[g].aln.npat; taxa.insert(store.items[g].aln.names.begin(), store.items[g].aln.names.end()); }
+                const size_t mp = std::max<size_t>(32, (pats + 31) / 32 * 32), nt = std::max<size_t>(taxa.size(), 3), groups = pars_radius > 0 ? 64 : 1;
+                return (nt + 3 * (nt - 2) + groups * (size_t)(pars_radius + 2)) * mp * 4 + mp * 4;
+            };
+            if (support_method == PML_TREE_PARSIMONY && ctx->c.arena_cache) {
+                // the pools are allocations of their own: the full tree's arena goes back to the driver, as the budget counts it
+                hipFree(ctx->c.arena_cache); ctx->c.arena_cache = nullptr; ctx->c.arena_cache_bytes = 0;
+            }
+            for (int begin = 0; begin < reps_here && support_method == PML_TREE_PARSIMONY;) {
+                size_t used = 0; int end = begin;
+                while (end < reps_here) { const size_t need = pars_bytes(rep[end]); if (end > begin && used + need > budget) break; used += need; ++end; }
+                std::vector<std::vector<int>> part(rep.begin() + begin, rep.begin() + end);
+                std::vector<unsigned> seeds;
+                for (int r = begin; r < end; ++r) seeds.push_back(parsimony_seed(seed, 1 + draw_index(r)));
+                std::vector<Tree> pt; std::vector<std::vector<std::string>> pn; std::vector<long long> pl;
+                if (int rc = parsimony_replicates(&ctx->c, store, part, seeds, pars_radius, pt, pn, pl)) return rc;
+                for (int r = begin; r < end; ++r) {
+                    const std::string nw = pt[r - begin].newick(pn[r - begin], -1);       // topology only, as pml_parsimony prints
+                    sup_txt += nw; sup_txt += '\n';
+                    if (mp_out) mp_out[1 + draw_index(r)] = pl[r - begin];
+                    if (srank != 0 || rule != SUPPORT_EQUAL_TAXA) continue;
+                    if (pn[r - begin] == main_names) sup[r] = pt[r - begin];
+                    else { std::string e2; Tree t; if (Tree::parse(nw.c_str(), main_names, t, e2)) sup[r] = t; else sup[r] = Tree(); }
+                }
+                begin = end;
+            }
+            for (int begin = 0; begin < reps_here && support_method == PML_TREE_ML;) {
                 size_t used = 0; int end = begin;
                 while (end < reps_here) { const size_t need = rep_bytes(rep[end]); if (end > begin && used + need > budget) break; used += need; ++end; }
                 std::vector<std::vector<int>> part(rep.begin() + begin, rep.begin() + end);
@@ -214,8 +285,9 @@ static int jackknife_run(pml_ctx *ctx, int ngenes, const pml_alignment *genes, c
             for (auto &l : lines) ptrs.push_back(l.c_str());
             if (!support_counts_rule(main_tree, main_names, ptrs, rule, counts, err)) return ctx->c.fail(PML_EPARSE, err);
         }
-        const std::string out = srank == 0 ? main_tree.newick_labeled(main_names, 6, counts) : std::string();
-        main_out->lnl = main_lnl; main_out->alpha = main_alpha; main_out->tree_length = main_tree.length();
+        const bool topo_only = full_method == PML_TREE_PARSIMONY;          // a parsimony tree has no lengths: `)87`
+        const std::string out = srank == 0 ? main_tree.newick_labeled(main_names, topo_only ? -1 : 6, counts) : std::string();
+        main_out->lnl = main_lnl; main_out->alpha = main_alpha; main_out->tree_length = topo_only ? 0.0 : main_tree.length();
         main_out->npatterns = main_npat; main_out->nsites = main_nsites;
         if (srank == 0) main_out->newick = dup_cstr(out);
         if (support_out) *support_out = dup_cstr(sup_txt);
@@ -254,6 +326,58 @@ extern "C" int pml_jackknife2(pml_ctx *ctx, int ngenes, const pml_alignment *gen
         if (m && m->ncat != 1 && m->ncat != 4) return ctx->c.fail(PML_EINVAL, "ncat must be 1 or 4");
     }
     return jackknife_run(ctx, ngenes, genes, full_model, sm, rule, opts ? &opts->base : nullptr, main_out, support_out);
+}
+
+extern "C" int pml_jackknife3(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *full_model,
+                              const pml_jackknife_opts3 *opts, pml_result *main_out, char **support_out, long long *mp_lengths_out) {
+    if (!ctx || !genes || ngenes <= 0 || !main_out) return PML_EINVAL;
+    std::memset(main_out, 0, sizeof *main_out);
+    if (support_out) *support_out = nullptr;
+    const pml_jackknife_opts2 *o2 = opts ? &opts->base2 : nullptr;
+    const int rule = o2 ? o2->support_rule : PML_SUPPORT_EQUAL_TAXA;
+    const int fm = opts ? opts->full_method : PML_TREE_ML, sm_ = opts ? opts->support_method : PML_TREE_ML, radius = opts ? opts->parsimony_radius : 20;
+    const pml_model *sm = (o2 && o2->support_model) ? o2->support_model : full_model;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    // everything is refused here, before a gene is encoded or uploaded
+    if (rule != PML_SUPPORT_EQUAL_TAXA && rule != PML_SUPPORT_DECORATOR && rule != PML_SUPPORT_RESTRICTED) return ctx->c.fail(PML_EINVAL, "bad support_rule " + std::to_string(rule));
+    if (fm != PML_TREE_ML && fm != PML_TREE_PARSIMONY && fm != PML_TREE_PARSIMONY_BL) return ctx->c.fail(PML_EINVAL, "bad full_method " + std::to_string(fm));
+    if (sm_ == PML_TREE_PARSIMONY_BL)
+        return ctx->c.fail(PML_EINVAL, "support_method PML_TREE_PARSIMONY_BL is not built: nothing reads a support tree's branch lengths (use PML_TREE_PARSIMONY)");
+    if (sm_ != PML_TREE_ML && sm_ != PML_TREE_PARSIMONY) return ctx->c.fail(PML_EINVAL, "bad support_method " + std::to_string(sm_));
+    if (radius < 0) return ctx->c.fail(PML_EINVAL, "parsimony_radius must not be negative");
+    // a model is checked where a tree is built under it
+    const pml_model *used[2] = {fm == PML_TREE_PARSIMONY ? nullptr : full_model, sm_ == PML_TREE_PARSIMONY ? nullptr : sm};
+    for (const pml_model *m : used) {
+        if (m && !ctx->c.valid_code(m->pi_mode)) return ctx->c.fail(PML_EINVAL, "bad pi_mode " + std::to_string(m->pi_mode));
+        if (m && m->ncat != 1 && m->ncat != 4) return ctx->c.fail(PML_EINVAL, "ncat must be 1 or 4");
+    }
+    return jackknife_run(ctx, ngenes, genes, full_model, sm, rule, o2 ? &o2->base : nullptr, main_out, support_out, fm, sm_, radius, mp_lengths_out);
+}
+
+// Test hook for k_fitch_tips, as pml_debug_gather is for k_gather: the Fitch tip rows and weights of one gene selection, read back.
+extern "C" int pml_debug_fitch_tips(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nsel, const int *sel, int *ntax_out,
+                                    int *npat_out, int *mpad_out, unsigned **masks_out, int **weights_out, char **names_out) {
+    if (!ctx || !genes || ngenes <= 0 || !ntax_out || !npat_out || !mpad_out || !masks_out || !weights_out || !names_out || (sel && nsel <= 0)) return PML_EINVAL;
+    *masks_out = nullptr; *weights_out = nullptr; *names_out = nullptr;
+    std::lock_guard<std::mutex> lk(ctx->c.mu);
+    pml_drop_worker_caches(ctx);
+    try {
+        for (int g = 0; g < ngenes; ++g) if (!genes[g].names || !genes[g].rows || genes[g].ntax <= 0) return ctx->c.fail(PML_EINVAL, "bad alignment");
+        std::vector<int> s;
+        if (sel) s.assign(sel, sel + nsel); else { s.resize(ngenes); for (int i = 0; i < ngenes; ++i) s[i] = i; }
+        GeneStore store;
+        struct Drop { GeneStore &s; ~Drop() { s.destroy(); } } drop{store};
+        if (int rc = store.create(&ctx->c, ngenes, reinterpret_cast<const pml_alignment_view *>(genes))) return rc;
+        std::vector<unsigned> masks; std::vector<int> w; std::vector<std::string> nm;
+        if (int rc = fitch_tips_readback(&ctx->c, store, s, npat_out, mpad_out, masks, w, nm)) return rc;
+        unsigned *pm = (unsigned *)std::malloc(masks.size() * sizeof(unsigned)); int *pw = (int *)std::malloc(w.size() * sizeof(int));
+        if (!pm || !pw) { std::free(pm); std::free(pw); return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+        std::memcpy(pm, masks.data(), masks.size() * sizeof(unsigned)); std::memcpy(pw, w.data(), w.size() * sizeof(int));
+        std::string names; for (auto &n : nm) { names += n; names += '\n'; }
+        *ntax_out = (int)nm.size(); *masks_out = pm; *weights_out = pw; *names_out = dup_cstr(names);
+    } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+    catch (const std::exception &e) { return ctx->c.fail(PML_EINVAL, e.what()); }
+    return PML_OK;
 }
 
 // Test hook for k_codehist: the selection is gathered TOGETHER with the replicate of all genes (one batch, one k_codehist

@@ -15,6 +15,10 @@
 // Scores are reduced inside a wavefront (DPP) and stored per wave (no atomics); k_fitch_reduce sums
 // the waves.  The algorithm (addition order, enumeration orders, tie breaks) is the one spelled out in
 // oracle/pml_oracle.c so results are bit-identical to the oracle.
+//
+// The tip vectors come from one of two sources: alignment text encoded on the host (pml_parsimony*), or the genes that a
+// jackknife keeps resident in HBM (GeneStore): k_fitch_tips writes the tip rows and weights of every replicate of a
+// sub-batch straight from the genes' code matrices, one launch, no concatenated text and no replicate code matrix.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -33,6 +37,21 @@ struct FRed { const int *partial; int *out; int nscores, nwaves; };
 
 typedef const unsigned __attribute__((address_space(1))) *gcu32;
 typedef unsigned __attribute__((address_space(1))) *gu32;
+
+// state set of an alignment code (host.hpp aa_code): the one table of the text path and of k_fitch_tips
+__host__ __device__ __forceinline__ unsigned code_mask(int c) {
+    if (c < 20) return 1u << c;
+    if (c == 20) return (1u << 2) | (1u << 3);     // B = N | D
+    if (c == 21) return (1u << 5) | (1u << 6);     // Z = Q | E
+    return 0xFFFFFu;
+}
+// one (replicate, gene) segment of k_fitch_tips: patterns [0, npat) of the gene go to [dst_off, dst_off + npat) of the replicate's
+// tip rows and weights; rowmap[t] = the gene's row of replicate taxon t, -1 = the gene lacks it.  src == null: the padding
+// segment [dst_off, dst_off + npat) = [sum of npat, mpad) of the replicate, every set bit and weight 0
+struct FTipSeg {
+    const uint8_t *src; const double *w; const int *rowmap; unsigned *pool; int *dst_w;
+    int src_mpad, npat, mpad, dst_off, ntax_dst, pad;
+};
 
 __device__ __forceinline__ unsigned fitch(unsigned l, unsigned r) { const unsigned x = l & r; return x ? x : (l | r); }
 
@@ -90,16 +109,25 @@ __global__ __launch_bounds__(256) void k_fitch_reduce(const FRed *__restrict__ r
     }
 }
 
+// Tip vectors and weights of gathered replicates: blockIdx.x = segment, blockIdx.y = block of 256 patterns.  A thread owns a
+// pattern and walks the replicate's rows, so a wavefront stores 256 contiguous bytes per row (dst_off is arbitrary: dword
+// stores).  Byte reads, dword writes, HBM-bound; no atomics, nothing waits, every index is bounded by the descriptor.
+__global__ __launch_bounds__(256) void k_fitch_tips(const FTipSeg *__restrict__ segs) {
+    const FTipSeg s = segs[blockIdx.x];
+    const int p = blockIdx.y * 256 + threadIdx.x;
+    if (p >= s.npat) return;
+    const size_t d = (size_t)s.dst_off + p;                   // < mpad: dst_off + npat <= mpad
+    s.dst_w[d] = s.src ? (int)s.w[p] : 0;
+    for (int t = 0; t < s.ntax_dst; ++t) {
+        const int row = s.src ? s.rowmap[t] : -1;
+        s.pool[(size_t)t * s.mpad + d] = row >= 0 ? code_mask(s.src[(size_t)row * s.src_mpad + p]) : 0xFFFFFu;
+    }
+}
+
 #define PCHK(expr)                                                                                 \
     do { hipError_t e_ = (expr);                                                                   \
          if (e_ != hipSuccess) return ctx->fail(-4, std::string("parsimony: ") + hipGetErrorString(e_)); } while (0)
 
-static unsigned code_mask(int c) {
-    if (c < 20) return 1u << c;
-    if (c == 20) return (1u << 2) | (1u << 3);     // B = N | D
-    if (c == 21) return (1u << 5) | (1u << 6);     // Z = Q | E
-    return 0xFFFFFu;
-}
 static uint64_t splitmix(uint64_t &s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -151,6 +179,7 @@ struct Stage {
     }
     ~Stage() { if (d) hipFree(d); }
 };
+struct FreePools { std::vector<PGene> &G; ~FreePools() { for (auto &g : G) { if (g.d_pool) hipFree(g.d_pool); if (g.d_w) hipFree(g.d_w); } } };
 }  // namespace
 
 // one device step: runs[i] walks ops_of[i]; returns the reduced scores of every run
@@ -176,6 +205,7 @@ static int fitch_step(Ctx *ctx, Stage &st, Stage &sc, const std::vector<PGene *>
     }
     PCHK(hipMemcpyAsync(st.d, h.data(), total, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_fitch, dim3((max_mpad + 255) / 256, (unsigned)nr), dim3(256), 0, ctx->stream, (const FRun *)((char *)st.d + o_runs));
+    ctx->fitch_launches++;
     if (nsc) hipLaunchKernelGGL(k_fitch_reduce, dim3(std::min(64, (max_sc + 255) / 256), (unsigned)nr), dim3(256), 0, ctx->stream, (const FRed *)((char *)st.d + o_reds));
     PCHK(hipGetLastError());
     std::vector<int> flat(nsc);
@@ -187,36 +217,93 @@ static int fitch_step(Ctx *ctx, Stage &st, Stage &sc, const std::vector<PGene *>
     return 0;
 }
 
-// Parsimony trees of n genes: randomised stepwise addition (seed 0 = input order) + SPR hill climbing
-// within `radius` edges (0 = none).  trees_out[g] has branch lengths 0.1; lengths_out[g] = weighted Fitch length.
-int parsimony_batch(Ctx *ctx, int n, const pml_alignment_view *alns, unsigned seed, int radius,
-                    std::vector<Tree> &trees_out, std::vector<EncodedAlignment> &alns_out, std::vector<long long> &lengths_out, std::vector<int> &moves_out) {
-    std::vector<PGene> G(n);
-    Stage st{ctx}, sc{ctx};
+// The Fitch pools of a batch whose genes know ntax and mpad: the prune groups of the batch, then per gene the pool
+// (tips, 3 messages per inner node, radius + 2 path vectors per group) and the weights.  Nothing is filled here.
+static int alloc_pools(Ctx *ctx, std::vector<PGene> &G, int radius) {
     size_t total_blocks = 0;
-    for (int g = 0; g < n; ++g) {
-        std::string err;
-        if (!G[g].aln.encode(alns[g].ntax, alns[g].nsites, alns[g].names, alns[g].rows, err)) return ctx->fail(-2, "gene " + std::to_string(g) + ": " + err);
-        if (G[g].aln.ntax < 3) return ctx->fail(-2, "gene " + std::to_string(g) + ": parsimony needs at least 3 taxa");
-        total_blocks += (G[g].aln.mpad + 255) / 256;
-    }
+    for (auto &pg : G) total_blocks += (pg.aln.mpad + 255) / 256;
     // groups: independent prunes of one gene spread over several workgroups when the batch alone cannot fill 256 CUs
     const int want_groups = radius > 0 ? (int)std::max<size_t>(1, std::min<size_t>(64, (2048 + total_blocks - 1) / std::max<size_t>(total_blocks, 1))) : 1;
-    struct Free { std::vector<PGene> &G; ~Free() { for (auto &g : G) { if (g.d_pool) hipFree(g.d_pool); if (g.d_w) hipFree(g.d_w); } } } freer{G};
-    for (int g = 0; g < n; ++g) {
-        PGene &pg = G[g]; const int nt = pg.aln.ntax, mp = pg.aln.mpad;
+    for (auto &pg : G) {
+        const int nt = pg.aln.ntax, mp = pg.aln.mpad;
         pg.ngroups = want_groups; pg.nwaves = ((mp + 255) / 256) * 4;
         pg.nvec = nt + 3 * (nt - 2) + pg.ngroups * (radius + 2);
         PCHK(hipMalloc((void **)&pg.d_pool, (size_t)pg.nvec * mp * sizeof(unsigned)));
         PCHK(hipMalloc((void **)&pg.d_w, (size_t)mp * sizeof(int)));
-        std::vector<unsigned> tips((size_t)nt * mp); std::vector<int> w(mp);
-        for (size_t i = 0; i < tips.size(); ++i) tips[i] = code_mask(pg.aln.codes[i]);
-        for (int p = 0; p < mp; ++p) w[p] = (int)pg.aln.weight[p];
-        PCHK(hipMemcpy(pg.d_pool, tips.data(), tips.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        PCHK(hipMemcpy(pg.d_w, w.data(), w.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// Tip source of the jackknife: G[r] = the replicate of store genes sel[r] (taxa = sorted union of the genes' names, patterns =
+// the genes' patterns one after the other in selection order, as k_gather lays a replicate out; mpad = the next multiple of
+// 32), its pool allocated and its tip rows and weights, padding included, written by ONE k_fitch_tips launch for all of G
+static int replicate_tips(Ctx *ctx, const GeneStore &store, const std::vector<std::vector<int>> &sel, int radius, std::vector<PGene> &G) {
+    const int n = (int)sel.size();
+    G.resize(n);
+    struct SegH { int rep, gene, off; size_t rowmap_off; };
+    std::vector<SegH> segs; std::vector<int> rowmaps;
+    int max_npat = 0;
+    for (int r = 0; r < n; ++r) {
+        EncodedAlignment &A = G[r].aln;
+        for (int g : sel[r]) {
+            if (g < 0 || g >= (int)store.items.size()) return ctx->fail(-1, "gene index out of range");
+            A.names.insert(A.names.end(), store.items[g].aln.names.begin(), store.items[g].aln.names.end());
+        }
+        std::sort(A.names.begin(), A.names.end()); A.names.erase(std::unique(A.names.begin(), A.names.end()), A.names.end());
+        const int nt = A.ntax = (int)A.names.size();
+        if (nt < 3) return ctx->fail(-2, "replicate " + std::to_string(r) + ": parsimony needs at least 3 taxa");
+        for (int g : sel[r]) {
+            const EncodedAlignment &S = store.items[g].aln;
+            SegH sh{r, g, A.npat, rowmaps.size()};
+            rowmaps.resize(rowmaps.size() + nt, -1);
+            for (int i = 0; i < S.ntax; ++i) rowmaps[sh.rowmap_off + (size_t)(std::lower_bound(A.names.begin(), A.names.end(), S.names[i]) - A.names.begin())] = i;
+            segs.push_back(sh);
+            A.npat += S.npat; A.nsites += S.nsites; max_npat = std::max(max_npat, S.npat);
+        }
+        A.mpad = std::max(32, (A.npat + 31) / 32 * 32);
+        if (A.mpad > A.npat) { segs.push_back(SegH{r, -1, A.npat, 0}); max_npat = std::max(max_npat, A.mpad - A.npat); }   // the padding segment
+    }
+    if (int rc = alloc_pools(ctx, G, radius)) return rc;
+    std::vector<FTipSeg> hs(segs.size());
+    const size_t seg_bytes = align_up(hs.size() * sizeof(FTipSeg), 256), map_bytes = rowmaps.size() * sizeof(int);
+    Stage buf{ctx};
+    if (int rc = buf.ensure(seg_bytes + map_bytes)) return rc;
+    const int *d_maps = (const int *)((char *)buf.d + seg_bytes);
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const PGene &pg = G[segs[i].rep];
+        if (segs[i].gene < 0) { hs[i] = FTipSeg{nullptr, nullptr, nullptr, pg.d_pool, pg.d_w, 0, pg.aln.mpad - pg.aln.npat, pg.aln.mpad, segs[i].off, pg.aln.ntax, 0}; continue; }
+        const GeneStore::Item &it = store.items[segs[i].gene];
+        hs[i] = FTipSeg{it.d_codes, it.d_w, d_maps + segs[i].rowmap_off, pg.d_pool, pg.d_w, it.aln.mpad, it.aln.npat, pg.aln.mpad, segs[i].off, pg.aln.ntax, 0};
+    }
+    PCHK(hipMemcpyAsync(buf.d, hs.data(), hs.size() * sizeof(FTipSeg), hipMemcpyHostToDevice, ctx->stream));
+    if (map_bytes) PCHK(hipMemcpyAsync((char *)buf.d + seg_bytes, rowmaps.data(), map_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const bool timed = std::getenv("PML_TRACE") != nullptr;        // diagnostic: the launch's HIP-event time
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    if (timed) { PCHK(hipEventCreate(&ev_a)); PCHK(hipEventCreate(&ev_b)); PCHK(hipEventRecord(ev_a, ctx->stream)); }
+    hipLaunchKernelGGL(k_fitch_tips, dim3((unsigned)hs.size(), (unsigned)((max_npat + 255) / 256)), dim3(256), 0, ctx->stream, (const FTipSeg *)buf.d);
+    if (timed) hipEventRecord(ev_b, ctx->stream);
+    ctx->fitch_tips_launches++;
+    PCHK(hipGetLastError());
+    if (int rc_ = ctx->sync(ctx->stream)) return rc_;               // the descriptors are freed on return
+    if (timed) {
+        float ms = 0; hipEventElapsedTime(&ms, ev_a, ev_b); hipEventDestroy(ev_a); hipEventDestroy(ev_b);
+        size_t cells = 0; for (auto &pg : G) cells += (size_t)pg.aln.ntax * pg.aln.mpad;
+        fprintf(stderr, "[pml] k_fitch_tips: %d replicates, %zu segments, %zu tip cells, %.3f ms\n", n, hs.size(), cells, ms);
+    }
+    return 0;
+}
+
+// The core: randomised stepwise addition (seed 0 = input order; a seed per gene) + SPR hill climbing within `radius` edges
+// (0 = none) over genes that hold their pool (tip rows filled), weights, ntax, mpad and names -- no host-side codes.
+// Every tree gets branch lengths 0.1; lengths_out[g] = weighted Fitch length.
+static int parsimony_core(Ctx *ctx, std::vector<PGene> &G, const std::vector<unsigned> &seeds, int radius, std::vector<long long> &lengths_out, std::vector<int> &moves_out) {
+    const int n = (int)G.size();
+    Stage st{ctx}, sc{ctx};
+    for (int g = 0; g < n; ++g) {
+        PGene &pg = G[g]; const int nt = pg.aln.ntax;
         pg.order.resize(nt);
         for (int i = 0; i < nt; ++i) pg.order[i] = i;
-        if (seed) { uint64_t s = seed; for (int i = nt - 1; i >= 1; --i) std::swap(pg.order[i], pg.order[(int)(splitmix(s) % (uint64_t)(i + 1))]); }
+        if (seeds[g]) { uint64_t s = seeds[g]; for (int i = nt - 1; i >= 1; --i) std::swap(pg.order[i], pg.order[(int)(splitmix(s) % (uint64_t)(i + 1))]); }
         Tree &t = pg.tree; t.ntax = nt;
         t.nbr.assign(2 * nt - 2, {-1, -1, -1}); t.len.assign(2 * nt - 2, {0.1, 0.1, 0.1});
         for (int k = 0; k < 3; ++k) { t.nbr[nt][k] = pg.order[k]; t.nbr[pg.order[k]][0] = nt; }
@@ -328,8 +415,66 @@ int parsimony_batch(Ctx *ctx, int n, const pml_alignment_view *alns, unsigned se
     owner.clear(); ops_of.clear(); nscores.clear();
     for (auto &pg : G) { std::vector<FOp> ops; int ns = 0; pg.refresh_ops(0, ops, &ns); owner.push_back(&pg); ops_of.push_back(std::move(ops)); nscores.push_back(ns); }
     if (int rc = fitch_step(ctx, st, sc, owner, ops_of, nscores, scores)) return rc;
-    trees_out.resize(n); alns_out.resize(n); lengths_out.assign(n, 0);
-    for (int g = 0; g < n; ++g) { for (int v : scores[g]) lengths_out[g] += v; trees_out[g] = G[g].tree; alns_out[g] = std::move(G[g].aln); }
+    lengths_out.assign(n, 0);
+    for (int g = 0; g < n; ++g) for (int v : scores[g]) lengths_out[g] += v;
+    return 0;
+}
+
+// Parsimony trees of n genes given as text (pml_parsimony*, the parsimony start of pml_search): the tip rows are filled on
+// the host from the encoded alignment, then the core runs with one seed for all genes.
+int parsimony_batch(Ctx *ctx, int n, const pml_alignment_view *alns, unsigned seed, int radius,
+                    std::vector<Tree> &trees_out, std::vector<EncodedAlignment> &alns_out, std::vector<long long> &lengths_out, std::vector<int> &moves_out) {
+    std::vector<PGene> G(n);
+    for (int g = 0; g < n; ++g) {
+        std::string err;
+        if (!G[g].aln.encode(alns[g].ntax, alns[g].nsites, alns[g].names, alns[g].rows, err)) return ctx->fail(-2, "gene " + std::to_string(g) + ": " + err);
+        if (G[g].aln.ntax < 3) return ctx->fail(-2, "gene " + std::to_string(g) + ": parsimony needs at least 3 taxa");
+    }
+    FreePools freer{G};
+    if (int rc = alloc_pools(ctx, G, radius)) return rc;
+    for (auto &pg : G) {
+        const int nt = pg.aln.ntax, mp = pg.aln.mpad;
+        std::vector<unsigned> tips((size_t)nt * mp); std::vector<int> w(mp);
+        for (size_t i = 0; i < tips.size(); ++i) tips[i] = code_mask(pg.aln.codes[i]);
+        for (int p = 0; p < mp; ++p) w[p] = (int)pg.aln.weight[p];
+        PCHK(hipMemcpy(pg.d_pool, tips.data(), tips.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        PCHK(hipMemcpy(pg.d_w, w.data(), w.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (int rc = parsimony_core(ctx, G, std::vector<unsigned>((size_t)n, seed), radius, lengths_out, moves_out)) return rc;
+    trees_out.resize(n); alns_out.resize(n);
+    for (int g = 0; g < n; ++g) { trees_out[g] = G[g].tree; alns_out[g] = std::move(G[g].aln); }
+    return 0;
+}
+
+// Parsimony trees of gene selections over a resident gene store (the jackknife's replicates and its full tree): tips by
+// k_fitch_tips, then the same core in lock step with a seed per replicate.  names_out[r] = the replicate's sorted taxon union.
+int parsimony_replicates(Ctx *ctx, const GeneStore &store, const std::vector<std::vector<int>> &selections, const std::vector<unsigned> &seeds,
+                         int radius, std::vector<Tree> &trees_out, std::vector<std::vector<std::string>> &names_out, std::vector<long long> &lengths_out) {
+    const int n = (int)selections.size();
+    if (n <= 0 || seeds.size() != selections.size()) return ctx->fail(-1, "parsimony: a seed per selection");
+    PCHK(hipSetDevice(ctx->device));
+    std::vector<PGene> G;
+    FreePools freer{G};
+    if (int rc = replicate_tips(ctx, store, selections, radius, G)) return rc;
+    std::vector<int> moves;
+    if (int rc = parsimony_core(ctx, G, seeds, radius, lengths_out, moves)) return rc;
+    trees_out.resize(n); names_out.resize(n);
+    for (int g = 0; g < n; ++g) { trees_out[g] = G[g].tree; names_out[g] = std::move(G[g].aln.names); }
+    return 0;
+}
+
+// pml_debug_fitch_tips: what k_fitch_tips wrote for one selection, read back -- the pool's tip rows [ntax x mpad] and the weights [mpad]
+int fitch_tips_readback(Ctx *ctx, const GeneStore &store, const std::vector<int> &sel, int *npat_out, int *mpad_out, std::vector<unsigned> &masks_out,
+                        std::vector<int> &weights_out, std::vector<std::string> &names_out) {
+    PCHK(hipSetDevice(ctx->device));
+    std::vector<PGene> G;
+    FreePools freer{G};
+    if (int rc = replicate_tips(ctx, store, {sel}, 0, G)) return rc;
+    const PGene &pg = G[0];
+    masks_out.resize((size_t)pg.aln.ntax * pg.aln.mpad); weights_out.resize((size_t)pg.aln.mpad);
+    PCHK(hipMemcpy(masks_out.data(), pg.d_pool, masks_out.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    PCHK(hipMemcpy(weights_out.data(), pg.d_w, weights_out.size() * sizeof(int), hipMemcpyDeviceToHost));
+    *npat_out = pg.aln.npat; *mpad_out = pg.aln.mpad; names_out = pg.aln.names;
     return 0;
 }
 

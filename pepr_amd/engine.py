@@ -16,6 +16,7 @@ RADIUS_FIXED, RADIUS_AUTO, SPR_RADIUS_MAX = 0, 1, 25       # pml_search_opts2.ra
 PI_GTR = 3             # PROTGAMMAGTR: exchangeabilities estimated per gene by the optimising calls, empirical frequencies
 NJ_DISTANCE, NJ_SIMILARITY = 0, 1      # pml_nj_from_matrix matrix types (TreeBuilder.DISTANCE / SIMILARITY)
 NJ_TREE, NJ_TOPOLOGY = 0, 1            # getNJTreeString (lengths) / getNJTopology (the `-nj true` path)
+TREE_ML, TREE_PARSIMONY, TREE_PARSIMONY_BL = 0, 1, 2      # pml_jackknife3 tree-building methods (PML_TREE_*)
 EINVAL = -1
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
@@ -394,6 +395,61 @@ class Context:
         if sup:
             self.L.pml_free(sup)
         return out
+
+    def jackknife3(self, genes, reps=100, subset_size=0, seed=0, spr_radius_full=5, epsilon=1e-3, alpha=1.0, ncat=4,
+                   pi_mode=PI_RAXML_3DP, support_pi_mode=None, support_alpha=None, support_rule=SUPPORT_EQUAL_TAXA, shard=(0, 1),
+                   full_method=TREE_ML, support_method=TREE_ML, parsimony_radius=20):
+        """jackknife2() with a tree-building method for the full tree (TREE_ML, TREE_PARSIMONY, TREE_PARSIMONY_BL) and for the
+        support trees (TREE_ML, TREE_PARSIMONY): parsimony trees are built from the genes resident in HBM (k_fitch_tips) and
+        come back topology only.  -> jackknife2's dict plus "mp_lengths": 1 + reps Fitch lengths, [0] the full tree, [1 + r]
+        replicate r of jackknife_draw's list; -1 = not a parsimony tree, or not built on this rank."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        m = _model(ncat, alpha, pi_mode)
+        sm = None
+        if support_pi_mode is not None or support_alpha is not None:
+            sm = _model(ncat, alpha if support_alpha is None else support_alpha, pi_mode if support_pi_mode is None else support_pi_mode)
+        o2 = _lib.JackknifeOpts2(_lib.JackknifeOpts(reps, subset_size, seed, spr_radius_full, epsilon, int(shard[0]), int(shard[1])),
+                                 C.pointer(sm) if sm is not None else None, int(support_rule))
+        o = _lib.JackknifeOpts3(o2, int(full_method), int(support_method), int(parsimony_radius), 0)
+        res = _lib.Result()
+        sup = C.c_void_p()
+        mp = (C.c_longlong * (1 + max(reps, 0)))()
+        rc = self.L.pml_jackknife3(self.ptr, n, alns, C.byref(m), C.byref(o), C.byref(res), C.byref(sup), mp)
+        self._check(rc)
+        out = {"lnl": res.lnl, "alpha": res.alpha, "tree_length": res.tree_length, "npatterns": res.npatterns,
+               "nsites": res.nsites, "newick": C.string_at(res.newick).decode() if res.newick else None,
+               "support_trees": C.string_at(sup).decode().splitlines() if sup else [], "mp_lengths": [int(v) for v in mp]}
+        self.L.pml_result_free(C.byref(res))
+        if sup:
+            self.L.pml_free(sup)
+        return out
+
+    def fitch_stats(self):
+        """k_fitch_tips and k_fitch launches on this context so far"""
+        a, b = C.c_longlong(), C.c_longlong()
+        self._check(self.L.pml_fitch_stats(self.ptr, C.byref(a), C.byref(b)))
+        return {"tips_launches": a.value, "fitch_launches": b.value}
+
+    def debug_fitch_tips(self, genes, sel=None):
+        """Test hook for k_fitch_tips: the Fitch tip vectors it writes for the gene selection, read back, padding included
+        -> (names, masks uint32[ntax, mpad], weights int32[mpad], npat)."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        nt, npat, mpad = C.c_int(), C.c_int(), C.c_int()
+        masks, w, names = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        arr = (C.c_int * len(sel))(*sel) if sel is not None else None
+        rc = self.L.pml_debug_fitch_tips(self.ptr, n, alns, len(sel) if sel is not None else 0, arr, C.byref(nt), C.byref(npat),
+                                         C.byref(mpad), C.byref(masks), C.byref(w), C.byref(names))
+        self._check(rc)
+        mm = np.frombuffer(C.string_at(masks, 4 * nt.value * mpad.value), dtype=np.uint32).reshape(nt.value, mpad.value).copy()
+        wv = np.frombuffer(C.string_at(w, 4 * mpad.value), dtype=np.int32).copy()
+        nm = C.string_at(names).decode().splitlines()
+        for p in (masks, w, names):
+            self.L.pml_free(p)
+        return nm, mm, wv, npat.value
 
     # ---- the reference's `nj` method: BLOSUM62 pair scores on the device (k_pairscore), TreeBuilder's NJ on the host ----
     def pairwise_scores(self, gene, table=None):
@@ -990,6 +1046,15 @@ def jackknife_draw(ngenes, reps, subset_size=0, seed=0):
         raise PmlError(rc)
     assert rc == k
     return [list(out[r * k:(r + 1) * k]) for r in range(reps)]
+
+
+def jackknife_parsimony_seeds(seed, reps):
+    """Host only: the stepwise-addition seeds of pml_jackknife3's parsimony trees -> (full tree's seed, [replicate r's seed]):
+    (unsigned)seed and (unsigned)(seed + 1 + r), r = the replicate's index in jackknife_draw's list; 0 ("input order" to
+    pml_parsimony) is replaced by 0x9E3779B9."""
+    def u32(v):
+        return (v & 0xFFFFFFFF) or 0x9E3779B9
+    return u32(seed), [u32(seed + 1 + r) for r in range(reps)]
 
 
 def congruence_select(mean_costs, trim_percent=0.1):

@@ -470,14 +470,23 @@ def buildConcatenatedTreeWithGeneWiseJackKnifeSupport(genes, reps=100, supportTr
     support_rule.  fullTreeMethod "nj" (`-full_tree_method nj`, with "nj" support trees): the whole loop is pml_nj_jackknife,
     and "newick" is the NJ tree's own text with the counts behind its inner nodes; with ML or FastTree support trees it is
     refused (that loop would search a full ML tree only to drop it).
+    supportTreeMethod "parsimony" and fullTreeMethod "parsimony" / "parsimony_bl" (`raxmlHPC -y`, and `-y` then `-f e -t`,
+    PhylogeneticTreeBuilder.java:104-115,136-161) go through pml_jackknife3: parsimony trees of the genes resident in HBM,
+    topology only (RAxML's radius 20); "parsimony_bl" optimises the full tree's lengths and alpha under mlMatrix.  A
+    "parsimony_bl" support tree is refused (nothing reads a support tree's lengths), as is a "FastTree" full tree (its Gamma20
+    rescale is not built into the loop).  These calls also return "mp_lengths" (Context.jackknife3).
     -> the dict of Context.jackknife2: "newick" carries the supports, "support_trees" the replicate trees (the NJ loop
     returns these two keys alone: an NJ tree has no likelihood)."""
-    if supportTreeMethod not in (ML, FAST_TREE, NEIGHBOR_JOINING):
-        raise ValueError("support tree method %r is outside the GPU path (ml, FastTree, nj)" % supportTreeMethod)
-    if fullTreeMethod not in (ML, NEIGHBOR_JOINING):
-        raise ValueError("full tree method %r is not built here (ml, nj)" % fullTreeMethod)
+    if supportTreeMethod == PARSIMONY_BL:
+        raise ValueError("support tree method 'parsimony_bl' is not built: nothing reads a support tree's branch lengths (use 'parsimony')")
+    if supportTreeMethod not in (ML, FAST_TREE, PARSIMONY, NEIGHBOR_JOINING):
+        raise ValueError("support tree method %r is outside the GPU path (ml, FastTree, parsimony, nj)" % supportTreeMethod)
+    if fullTreeMethod not in (ML, PARSIMONY, PARSIMONY_BL, NEIGHBOR_JOINING):
+        raise ValueError("full tree method %r is not built here (ml, parsimony, parsimony_bl, nj)" % fullTreeMethod)
     if fullTreeMethod == NEIGHBOR_JOINING and supportTreeMethod != NEIGHBOR_JOINING:
         raise ValueError("an nj full tree takes nj support trees (support tree method %r would search a full ML tree to drop it)" % supportTreeMethod)
+    if fullTreeMethod in (PARSIMONY, PARSIMONY_BL) and supportTreeMethod == NEIGHBOR_JOINING:
+        raise ValueError("nj support trees under a %s full tree are not built (nj support trees take an ml or nj full tree)" % fullTreeMethod)
     full = _model_from_matrix(mlMatrix, ctx)                        # an unbuilt model name is refused before any device work
     support_pi = full["pi_mode"] if supportTreeMethod == ML else engine.PI_WAG_FULL
     ctx = ctx or default_context()
@@ -490,5 +499,10 @@ def buildConcatenatedTreeWithGeneWiseJackKnifeSupport(genes, reps=100, supportTr
         r["support_trees"] = ctx.nj_replicates(pairs, sel, form=engine.NJ_TREE) if reps > 0 else []
         r["newick"] = engine.support_tree_rule(r["newick"], r["support_trees"], support_rule)
         return r
+    if PARSIMONY in (supportTreeMethod, fullTreeMethod) or fullTreeMethod == PARSIMONY_BL:
+        methods = {ML: engine.TREE_ML, FAST_TREE: engine.TREE_ML, PARSIMONY: engine.TREE_PARSIMONY, PARSIMONY_BL: engine.TREE_PARSIMONY_BL}
+        return ctx.jackknife3(pairs, reps=reps, seed=seed, spr_radius_full=5, pi_mode=full["pi_mode"], ncat=full["ncat"],
+                              support_pi_mode=support_pi, support_rule=support_rule, full_method=methods[fullTreeMethod],
+                              support_method=methods[supportTreeMethod], parsimony_radius=20)
     return ctx.jackknife2(pairs, reps=reps, seed=seed, spr_radius_full=5, pi_mode=full["pi_mode"], ncat=full["ncat"],
                           support_pi_mode=support_pi, support_rule=support_rule)

@@ -8,7 +8,7 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
     <run>.sup   the support trees, one Newick per line
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
-                         [--full-tree-method ml|nj] [--support-tree-method ml|FastTree|nj]
+                         [--full-tree-method ml|parsimony|parsimony_bl|nj] [--support-tree-method ml|FastTree|parsimony|nj]
                          [-congruence_filter] [-trim_percent 0.1]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
@@ -19,7 +19,11 @@ usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-se
 --full-tree-method, --support-tree-method   PEPR's -full_tree_method / -support_tree_method; the value nj builds the trees by
                   neighbor joining on BLOSUM62 pair scores, as the reference's TreeBuilder does (supports under --support-rule,
                   default 1); nj for the full tree takes nj support trees (the default support method then); --support-matrix is
-                  refused with these two flags (ml support trees use --matrix, FastTree ones are WAG, nj has no model)
+                  refused with these two flags (ml support trees use --matrix, FastTree ones are WAG, nj has no model).
+                  The value parsimony builds the trees by maximum parsimony (`raxmlHPC -y`: stepwise addition + SPR radius 20)
+                  from the genes resident on the device; they are written topology only, so a parsimony full tree has supports
+                  but no lengths and no likelihood.  parsimony_bl (full tree only) then optimises branch lengths and alpha under
+                  --matrix (`-f e -t`).  parsimony_bl support trees and a FastTree full tree are refused
 -congruence_filter, -trim_percent P   PEPR's flags of the same names (HandyConstants.java:86, :92): before any tree is built the
                   genes are filtered as PhylogenomicPipeline2.filterForCongruence filters them (column bipartition costs, the
                   genes of the highest mean cost go; P of 1.0 or more is a percentage).  Prints the reference's two messages and
@@ -104,6 +108,10 @@ def main(argv):
     open(run + ".sup", "w").write("\n".join(r["support_trees"]) + "\n")
     if "lnl" not in r:                          # the NJ loop: no likelihood
         print("%s: %d genes, neighbor joining, %d support trees, %.2f s -> %s.nwk %s.sup" % (run, len(genes), reps, dt, run, run))
+        return
+    if r.get("mp_lengths") and r["mp_lengths"][0] >= 0 and ":" not in r["newick"]:      # a parsimony full tree: a Fitch length, no likelihood
+        print("%s: %d genes, %d columns, parsimony length %d, %d support trees, %.2f s -> %s.nwk %s.sup" % (
+            run, len(genes), r["nsites"], r["mp_lengths"][0], reps, dt, run, run))
         return
     print("%s: %d genes, %d columns, lnL %.3f, alpha %.4f, %d support trees, %.2f s -> %s.nwk %s.sup" % (
         run, len(genes), r["nsites"], r["lnl"], r["alpha"], reps, dt, run, run))
