@@ -14,6 +14,8 @@
  *   pml_*_batch    <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:1587-1633
  *                        GeneSubsetTreeRunnable.run(): the data-parallel loop of independent tree builds
  *   pml_rf_distance<- .../pepr/tree/AdvancedTree.java:1460-1491 (Robinson-Foulds used for acceptance)
+ *   pml_tree_compare<- .../pepr/tree/TreeComparison.java:267-288 compareAllvsAll(): legacy RF (Tree.java:589-603), the two
+ *                        branch distances (:607-810) and AdvancedTree's RF for every pair of a tree set, ONE call
  *   pml_jackknife  <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:994-1126
  *                        buildConcatenatedTreeWithGeneWiseJackKnifeSupport(): full tree + N support trees on
  *                        random gene subsets (:959-977, 1227-1275, 1587-1633) + support counts, ONE call
@@ -665,6 +667,73 @@ int  pml_debug_column_splits(pml_ctx *ctx, const pml_alignment *gene, int nunion
 /* the kept splits that k_splitcost holds in LDS at a time (tests size a case beyond it) */
 int  pml_congruence_ktile(void);
 
+/* TreeComparison's `-rf` and `-tree_dist` legs (TreeComparison.java:48-50, compareAllvsAll :267-288) for a whole set of trees:
+ * every pair (i, j), i < j, tree 1 = i, on the device (treecmp.hip).  The trees are given as Newick text and must all have the
+ * same leaf labels (PML_EINVAL otherwise; at most 512 leaves, at least 3).
+ *   model    what the Java compares is TreeParser.parseTreeString(BasicTree.getTreeString(useLengths, true)): one branch per node
+ *            below the top level, pendant branches included; a top level of two becomes ONE branch with the sum of the two
+ *            lengths, a top level of three becomes three branches; any other top level leaves the Java without a tree and is
+ *            PML_EINVAL here, as is a node with a single child (the Java's round trip corrupts its leaf's name).  A branch without
+ *            a length has length 0; use_lengths = 0 reads every length as 0; an inner node's label is its support and enters no
+ *            value.  Tree.getBranches() has no defined order in the Java (a HashSet of objects without hashCode); this library
+ *            uses the order in which TreeParser creates the branches: nodes in ascending index of the round-tripped text
+ *            (a node's leaves before its inner children; leaves in text order, inner nodes in the order of their ')'), then the
+ *            top-level branch or branches.  Only the rounding of the sums and, for a repeated split, the choice of the counterpart
+ *            depend on it.
+ *   rf_legacy       Tree.getRobinsonFouldsDistance (Tree.java:589-603): (|union| - |intersection|) / 4 over the sets that hold
+ *                   BOTH leaf sets of every branch = (dA + dB - 2 shared) / 2 over distinct splits, pendant ones included.
+ *   rf_bipartition  AdvancedTree.getRobinsonFouldsDistance (AdvancedTree.java:1460-1483): the same over non-trivial splits.
+ *   rf_splits       pml_rf_distance of the two texts: multifurcations resolved as Tree::parse resolves them.
+ *   branch_dist     getBranchDistance (TreeComparison.java:607-747): lengths over the tree's maximum; a branch's counterpart is
+ *                   the LAST branch of tree 2 with its split; sqrt(r) / sqrt(ss1 + ss2).  NaN when every length is 0.
+ *   discrepant_dist getDiscrepantBranchDistance (:756-810): raw lengths, unmatched branches only.
+ * The sums are accumulated on the device in the Java's order without fused multiply-adds; sqrt and the division are the host's.
+ * The diagonal holds 0 in the RF arrays and the formula's value of a tree against itself in the distances.  window = w > 0
+ * computes only |i - j| <= w (compareSlidingWindow :241-265, rollingComparison :457-466 are bands of the matrix); other entries
+ * hold -1 / NaN.  The trees' records stay in HBM for the call and the pair outputs are produced in blocks of rows that fit the
+ * budget (0.85 of free HBM, or PML_HBM_BUDGET_MB, which may be fractional here); a set whose records plus one row do not fit
+ * is PML_ENOMEM with the sizes.  compareBranchSupports (:374-454) is not part of this. */
+enum { PML_TC_RF_LEGACY = 1, PML_TC_RF_BIPARTITION = 2, PML_TC_RF_SPLITS = 4, PML_TC_BRANCH_DIST = 8, PML_TC_DISCREPANT_DIST = 16 };
+typedef struct {
+    int window;                       /* 0 = all pairs */
+    int use_lengths;                  /* TreeComparison's -use_lengths (the Java's default is true) */
+    int want;                         /* PML_TC_* bits of the arrays to produce; 0 = all */
+} pml_tree_compare_opts;
+typedef struct {
+    int nrows, ncols, ntax;           /* T x T (pml_tree_compare) or 1 x T (pml_tree_compare_one); row-major */
+    int *rf_legacy, *rf_bipartition, *rf_splits;      /* NULL when not wanted */
+    double *branch_dist, *discrepant_dist;
+    long long row_blocks;             /* k_tree_pairs launches of the call */
+    long long resident_bytes, row_bytes;              /* HBM held by the records; HBM per row of pair outputs */
+} pml_tree_compare_result;
+int  pml_tree_compare(pml_ctx *ctx, int ntrees, const char *const *newicks, const pml_tree_compare_opts *opts /* NULL: all pairs, lengths, all arrays */,
+                      pml_tree_compare_result *out);
+/* calculateTreeDistances (:557-565): the standard tree (tree 1) against each of the ntrees comparison trees; window is ignored */
+int  pml_tree_compare_one(pml_ctx *ctx, const char *standard_newick, int ntrees, const char *const *newicks, const pml_tree_compare_opts *opts,
+                          pml_tree_compare_result *out);
+void pml_tree_compare_result_free(pml_tree_compare_result *result);
+/* test door: the split records of a tree set as the kernels see them.  Tree t owns records first[t] .. first[t + 1] - 1; its
+ * first nreal[t] are its branches in branch order, the rest are the splits that resolving its multifurcations adds (rf_splits).
+ * split_words: W words per record over the sorted names, normalised (the side with fewer leaves, on a tie the side holding
+ * taxon 0); flags: 1 = a branch, 2 = trivial, 4 = the last record of its tree with its split; split_id: the index of the first
+ * record of the call with the same split. */
+typedef struct {
+    int ntrees, ntax, words;
+    char **names;
+    long long nrecords, *first;       /* [T + 1] */
+    int *nreal;                       /* [T] */
+    unsigned long long *split_words;  /* [nrecords][W] */
+    double *length, *length_norm;     /* [nrecords] */
+    int *flags, *split_id;            /* [nrecords] */
+} pml_tree_splits;
+int  pml_debug_tree_splits(pml_ctx *ctx, int ntrees, const char *const *newicks, int use_lengths, pml_tree_splits *out);
+void pml_tree_splits_free(pml_tree_splits *out);
+/* test door: what k_tree_pairs and k_tree_sums give for chosen pairs (i <= j): counts_out[p][7] = shared splits, shared
+ * non-trivial splits, shared splits of the resolved trees, distinct and distinct non-trivial splits of i, the same of j;
+ * sums_out[p][6] = r, sumOfSquaresTree1, sumOfSquaresTree2 of getBranchDistance, then of getDiscrepantBranchDistance */
+int  pml_debug_tree_pair_sums(pml_ctx *ctx, int ntrees, const char *const *newicks, int use_lengths, int npairs, const int *pairs /* [npairs][2] */,
+                              long long *counts_out, double *sums_out);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);
@@ -693,6 +762,9 @@ enum { PML_K_PMAT = 0, PML_K_NEWVIEW = 1, PML_K_EVALUATE = 2, PML_K_SUMTABLE = 3
        PML_K_COLSPLIT = 11 /* congruence filter: k_colsplits launches (count pass and write pass); bytes = alignment bytes read */,
        PML_K_SPLITCOST = 12 /* congruence filter: k_splitcost launches; bytes = split words read (distinct splits, and the kept set per workgroup) */,
        PML_K_COUNT = 13 };
+/* slots added after PML_K_COUNT was published (a client that sizes an array by it keeps working); PML_K_END is one past the last */
+enum { PML_K_TREEPAIRS = 13 /* tree-set comparison: k_tree_pairs launches (one per block of rows); bytes = 4 per set look-up */,
+       PML_K_END = 14 };
 int pml_kernel_stats(pml_ctx *ctx, int kernel, long long *launches, double *total_ms,
                      double *algo_bytes /* algorithmic bytes moved, SURVEY 8d figures */);
 /* algorithmic flops of the launches counted by pml_kernel_stats, SURVEY 8d's per-operation figures (newview inner-inner 6480,

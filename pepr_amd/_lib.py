@@ -29,7 +29,27 @@ SYMBOLS = [
     "pml_congruence_costs", "pml_congruence_result_free", "pml_congruence_select", "pml_congruence_filter", "pml_debug_column_splits",
     "pml_congruence_ktile",
     "pml_jackknife3", "pml_fitch_stats", "pml_debug_fitch_tips",
+    "pml_tree_compare", "pml_tree_compare_one", "pml_tree_compare_result_free", "pml_debug_tree_splits", "pml_tree_splits_free",
+    "pml_debug_tree_pair_sums",
 ]
+
+
+class TreeCompareOpts(C.Structure):
+    _fields_ = [("window", C.c_int), ("use_lengths", C.c_int), ("want", C.c_int)]
+
+
+class TreeCompareResult(C.Structure):
+    _fields_ = [("nrows", C.c_int), ("ncols", C.c_int), ("ntax", C.c_int),
+                ("rf_legacy", C.POINTER(C.c_int)), ("rf_bipartition", C.POINTER(C.c_int)), ("rf_splits", C.POINTER(C.c_int)),
+                ("branch_dist", C.POINTER(C.c_double)), ("discrepant_dist", C.POINTER(C.c_double)),
+                ("row_blocks", C.c_longlong), ("resident_bytes", C.c_longlong), ("row_bytes", C.c_longlong)]
+
+
+class TreeSplits(C.Structure):
+    _fields_ = [("ntrees", C.c_int), ("ntax", C.c_int), ("words", C.c_int), ("names", C.POINTER(C.c_char_p)),
+                ("nrecords", C.c_longlong), ("first", C.POINTER(C.c_longlong)), ("nreal", C.POINTER(C.c_int)),
+                ("split_words", C.POINTER(C.c_ulonglong)), ("length", C.POINTER(C.c_double)), ("length_norm", C.POINTER(C.c_double)),
+                ("flags", C.POINTER(C.c_int)), ("split_id", C.POINTER(C.c_int))]
 
 
 class Config(C.Structure):
@@ -241,5 +261,14 @@ def load():
     L.pml_jackknife3.argtypes = [vp, C.c_int, ap, mp, C.POINTER(JackknifeOpts3), rp, C.POINTER(vp), lp]
     L.pml_fitch_stats.argtypes = [vp, lp, lp]
     L.pml_debug_fitch_tips.argtypes = [vp, C.c_int, ap, C.c_int, ip, ip, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    tcp, tco = C.POINTER(TreeCompareResult), C.POINTER(TreeCompareOpts)
+    L.pml_tree_compare.argtypes = [vp, C.c_int, cpp, tco, tcp]
+    L.pml_tree_compare_one.argtypes = [vp, C.c_char_p, C.c_int, cpp, tco, tcp]
+    L.pml_tree_compare_result_free.argtypes = [tcp]
+    L.pml_tree_compare_result_free.restype = None
+    L.pml_debug_tree_splits.argtypes = [vp, C.c_int, cpp, C.c_int, C.POINTER(TreeSplits)]
+    L.pml_tree_splits_free.argtypes = [C.POINTER(TreeSplits)]
+    L.pml_tree_splits_free.restype = None
+    L.pml_debug_tree_pair_sums.argtypes = [vp, C.c_int, cpp, C.c_int, C.c_int, ip, lp, dp]
     _lib = L
     return L

@@ -14,7 +14,7 @@ namespace pml {
 
 constexpr int MAXTAIL = 4;            // tail requests (evaluate / sumtable+Newton) per gene per run()
 
-enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_CODEHIST = 9, K_PAIRSCORE = 10, K_COLSPLIT = 11, K_SPLITCOST = 12, K_COUNT = 13 };
+enum { K_PMAT = 0, K_NEWVIEW = 1, K_EVALUATE = 2, K_SUMTABLE = 3, K_NEWTON = 4, K_REDUCE = 5, K_HOST_BUILD = 6, K_HOST_WAIT = 7, K_MODEL = 8, K_CODEHIST = 9, K_PAIRSCORE = 10, K_COLSPLIT = 11, K_SPLITCOST = 12, K_TREEPAIRS = 13, K_COUNT = 14 };
 
 // Model codes (pml_model.pi_mode): 0 / 1 WAG with fixed frequencies, 2 WAG with the gene's empirical frequencies, 3 GTR
 // (exchangeabilities estimated per gene, empirical frequencies), 16 + 2 i the i-th registered matrix with its own

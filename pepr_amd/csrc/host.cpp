@@ -421,6 +421,16 @@ bool Tree::parse_free(const char *newick, std::vector<std::string> &names, Tree 
     return build_tree(P, root, tipid, (int)names.size(), out, err);
 }
 
+bool parse_newick_raw(const char *newick, std::vector<RawNode> &nodes, std::string &err) {
+    if (!newick) { err = "null newick"; return false; }
+    Parser P{newick};
+    const int root = P.subtree(0);
+    if (root < 0) { err = P.err; return false; }
+    nodes.clear(); nodes.reserve(P.nodes.size());
+    for (const RNode &r : P.nodes) { RawNode n; n.kids = r.kids; n.len = r.haslen ? r.len : 0.0; n.haslen = r.haslen; n.label = r.label; nodes.push_back(std::move(n)); }
+    return true;
+}
+
 double Tree::length() const {
     double s = 0;
     for (int i = 0; i < nnodes(); ++i) for (int k = 0; k < 3; ++k) if (nbr[i][k] > i) s += len[i][k];

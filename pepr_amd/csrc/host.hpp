@@ -58,6 +58,12 @@ struct Tree {
     std::string newick_labeled(const std::vector<std::string> &names, int digits, const std::vector<std::vector<double>> &edge_label, int label_digits) const;
 };
 
+// The Newick text as it stands, before Tree binarises it: node 0 is the root, a node's children in text order, parents before
+// children; haslen = the node carries ":length"; label = a leaf's name or an inner node's support text.  Same grammar as
+// Tree::parse (quotes, [..] comments, optional ';').  treecmp.cpp compares trees that keep their multifurcations.
+struct RawNode { std::vector<int> kids; double len = 0; bool haslen = false; std::string label; };
+bool parse_newick_raw(const char *newick, std::vector<RawNode> &nodes, std::string &err);
+
 int rf_distance(const Tree &a, const Tree &b);    // (|A|+|B|-2|A&B|)/2 over non-trivial splits
 // counts[u][k] = number of `others` containing the bipartition of main's internal edge (u, nbr[u][k]); -1 elsewhere
 std::vector<std::vector<int>> support_counts(const Tree &main, const std::vector<Tree> &others);

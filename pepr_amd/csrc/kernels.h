@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "treecmp.hpp"
+
 namespace pml {
 
 constexpr int NS = 20;                 // amino-acid states
@@ -226,6 +228,24 @@ void launch_splitcost(const unsigned long long *rec, const int *dist, long long 
 // cost_rec[id] and ndistinct[gene] += 1 once per distinct (gene, id)
 void launch_genecost(const int *rec_gene, const int *split_id, long long nrec, const long long *cost_rec, unsigned long long *keys,
                      unsigned long long cap, unsigned long long hash_mask, long long *cost_sum, int *ndistinct, int *err, hipStream_t s);
+
+// Tree-set comparison (treecmp.hip): the split records of T trees, compact: tree t owns entries off[t] .. off[t] + cnt[t] - 1 of
+// every array, its first nreal[t] are TreeBranches in the Java's order (treecmp.hpp).  id = interned split id, ln / lr =
+// length over the tree's maximum / the length itself, flags = TC_*; sid / sidx = the tree's (id, record index) pairs sorted
+// by id, for equal ids the highest index last (written by launch_tree_sort, which also sets TC_LAST).
+constexpr int TC_COLS = 256 /* column trees per k_tree_pairs workgroup, one per lane */, TC_SORT = 2048 /* keys k_tree_sort sorts in LDS: cnt[t] <= TC_SORT */;
+static_assert(3 * TC_MAX_TAXA <= TC_SORT && TC_MAX_TAXA == CG_MAX_TAXA && tc_words(200) == cg_words(200), "a tree has fewer than 3 n records");
+struct TcTrees { const int *off, *cnt, *nreal; int *id, *flags; const double *ln, *lr; int *sid, *sidx; int T; };
+// id[r] (the owner launch_split_intern gave) becomes the index of the FIRST record of its split; first[nrec] filled with 0x7F bytes by the caller
+void launch_tree_first(int *id, long long nrec, int *first, hipStream_t s);
+// sorts every tree's ids, sets TC_LAST, then ss[t] = {sum ln^2, sum lr^2} over the tree's branches in order and
+// distinct[t] = {distinct splits, distinct non-trivial splits} among them
+void launch_tree_sort(const TcTrees &t, double *ss, int *distinct, hipStream_t s);
+// rows i0 .. i0 + nrows - 1 against every column j >= i (window > 0: j - i <= window): counts[row * T + j] = {shared splits,
+// shared non-trivial splits, shared splits of the resolved trees (rf_splits), 0}, sums[row * T + j] = {r of getBranchDistance,
+// r of getDiscrepantBranchDistance}; other entries are not written.  maxrec >= every cnt[t] sizes the LDS (tree_pairs_lds)
+size_t tree_pairs_lds(int maxrec);
+void launch_tree_pairs(const TcTrees &t, int i0, int nrows, int window, int maxrec, int4 *counts, double2 *sums, hipStream_t s);
 
 // SH-like local support of one split (FastTree's SHSupport; Guindon et al. 2010): per-pattern lnL of the current
 // arrangement (l0) and of its two NNI alternatives (l1, l2); nboot resamples of nsites alignment columns drawn with

@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 
 KERNELS = {"pmat": 0, "newview": 1, "evaluate": 2, "sumtable": 3, "newton": 4, "reduce": 5,
-           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9, "pairscore": 10, "colsplit": 11, "splitcost": 12}
+           "host_build": 6, "host_wait": 7, "model": 8, "codehist": 9, "pairscore": 10, "colsplit": 11, "splitcost": 12, "treepairs": 13}
 PI_RAXML_3DP, PI_WAG_FULL, PI_EMPIRICAL = 0, 1, 2      # PI_EMPIRICAL = PROTGAMMAWAGF (frequencies counted per gene)
 SUPPORT_EQUAL_TAXA, SUPPORT_DECORATOR, SUPPORT_RESTRICTED = 0, 1, 2      # pml_jackknife2 / pml_support_tree_rule counting rules
 RADIUS_FIXED, RADIUS_AUTO, SPR_RADIUS_MAX = 0, 1, 25       # pml_search_opts2.radius_mode, PML_SPR_RADIUS_MAX
@@ -577,6 +577,78 @@ class Context:
         out["keep"] = [bool(f) for f in flags]
         return out
 
+    # ---- TreeComparison's -rf / -tree_dist legs for a set of trees (include/peprml.h pml_tree_compare) ----
+    TREE_COMPARE_ARRAYS = (("rf_legacy", 1, np.int32), ("rf_bipartition", 2, np.int32), ("rf_splits", 4, np.int32),
+                           ("branch_dist", 8, np.float64), ("discrepant_dist", 16, np.float64))
+
+    def _tree_compare_opts(self, window, use_lengths, want):
+        bits = 0
+        for name, bit, _ in self.TREE_COMPARE_ARRAYS:
+            if want is None or name in want:
+                bits |= bit
+        if want is not None and not bits:
+            raise ValueError("want names none of " + ", ".join(a[0] for a in self.TREE_COMPARE_ARRAYS))
+        return _lib.TreeCompareOpts(int(window), 1 if use_lengths else 0, bits)
+
+    def _tree_compare_result(self, res, one):
+        try:
+            shape = (res.ncols,) if one else (res.nrows, res.ncols)
+            out = {"ntax": res.ntax, "row_blocks": res.row_blocks, "resident_bytes": res.resident_bytes, "row_bytes": res.row_bytes}
+            for name, _, dt in self.TREE_COMPARE_ARRAYS:
+                p = getattr(res, name)
+                if p:
+                    out[name] = np.ctypeslib.as_array(p, shape=(res.nrows * res.ncols,)).astype(dt).reshape(shape)
+            return out
+        finally:
+            self.L.pml_tree_compare_result_free(C.byref(res))
+
+    def tree_compare(self, newicks, window=0, use_lengths=True, want=None):
+        """Every pair of a set of trees over one leaf set, as TreeComparison.compareAllvsAll computes it (tree 1 = the lower
+        index) -> {"rf_legacy", "rf_bipartition", "rf_splits": int32 [T, T]; "branch_dist", "discrepant_dist": float64 [T, T]}.
+        window = w > 0: only |i - j| <= w, the rest -1 / NaN.  want: the names of the arrays to produce (None = all)."""
+        o = self._tree_compare_opts(window, use_lengths, want)
+        na = (C.c_char_p * max(len(newicks), 1))(*[s.encode() for s in newicks])
+        res = _lib.TreeCompareResult()
+        self._check(self.L.pml_tree_compare(self.ptr, len(newicks), na, C.byref(o), C.byref(res)))
+        return self._tree_compare_result(res, False)
+
+    def tree_compare_one(self, standard, newicks, use_lengths=True, want=None):
+        """TreeComparison.calculateTreeDistances: the standard tree (tree 1) against each tree -> the same arrays, shape [T]"""
+        o = self._tree_compare_opts(0, use_lengths, want)
+        na = (C.c_char_p * max(len(newicks), 1))(*[s.encode() for s in newicks])
+        res = _lib.TreeCompareResult()
+        self._check(self.L.pml_tree_compare_one(self.ptr, standard.encode(), len(newicks), na, C.byref(o), C.byref(res)))
+        return self._tree_compare_result(res, True)
+
+    def debug_tree_splits(self, newicks, use_lengths=True):
+        """Test door: the split records of a tree set as the kernels see them -> {"names", "first" [T + 1], "nreal" [T], "splits"
+        (ints, taxon i = bit i), "length", "length_norm", "flags", "split_id"}, records in branch order per tree"""
+        na = (C.c_char_p * max(len(newicks), 1))(*[s.encode() for s in newicks])
+        res = _lib.TreeSplits()
+        self._check(self.L.pml_debug_tree_splits(self.ptr, len(newicks), na, 1 if use_lengths else 0, C.byref(res)))
+        try:
+            N, w, T = res.nrecords, res.words, res.ntrees
+            words = np.array(res.split_words[:N * w], dtype=np.uint64).reshape(N, w)
+            return {"names": [res.names[i].decode() for i in range(res.ntax)], "first": list(res.first[:T + 1]), "nreal": list(res.nreal[:T]),
+                    "splits": [sum(int(r[x]) << (64 * x) for x in range(w)) for r in words],
+                    "length": np.array(res.length[:N]), "length_norm": np.array(res.length_norm[:N]),
+                    "flags": list(res.flags[:N]), "split_id": list(res.split_id[:N]), "words": w}
+        finally:
+            self.L.pml_tree_splits_free(C.byref(res))
+
+    def debug_tree_pair_sums(self, newicks, pairs, use_lengths=True):
+        """Test door: the raw results of chosen pairs (i <= j, tree 1 = i) -> (counts int64 [P, 7], sums float64 [P, 6]): shared,
+        shared non-trivial, shared resolved, distinct / distinct non-trivial of i and of j; r, ss1, ss2 of getBranchDistance and
+        of getDiscrepantBranchDistance"""
+        na = (C.c_char_p * max(len(newicks), 1))(*[s.encode() for s in newicks])
+        P = len(pairs)
+        flat = (C.c_int * max(2 * P, 1))(*[int(x) for p in pairs for x in p])
+        counts = np.zeros((P, 7), dtype=np.int64)
+        sums = np.zeros((P, 6), dtype=np.float64)
+        self._check(self.L.pml_debug_tree_pair_sums(self.ptr, len(newicks), na, 1 if use_lengths else 0, P, flat,
+                                                    counts.ctypes.data_as(C.POINTER(C.c_longlong)), sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return counts, sums
+
     def debug_column_splits(self, gene, names_union):
         """Test hook of k_colsplits: the split records of one gene's columns over the sorted union as the kernel wrote them ->
         list of (column, split as an int with taxon i = bit i), in record order"""
@@ -967,6 +1039,21 @@ def au_fit(r, count, B):
     if rc:
         raise PmlError(rc)
     return {"au": au.value, "d": d.value, "c": c.value, "rss": rss.value, "nused": nused.value}
+
+
+def format_double(x):
+    """a double as text that reads back to the same bits: the shortest of %.15g, %.16g, %.17g that does (nj.hpp nj_number's
+    rule, the spelling of every number this project prints: `0` for Java's `0.0`); NaN and infinities as Java spells them"""
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (float("inf"), float("-inf")):
+        return "Infinity" if x > 0 else "-Infinity"
+    for p in (15, 16, 17):
+        s = "%.*g" % (p, x)
+        if float(s) == x:
+            return s
+    return s
 
 
 def rf_distance(newick_a, newick_b):

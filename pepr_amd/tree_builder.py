@@ -8,6 +8,10 @@ read like the reference's own call sites; every `run()` goes through the C ABI
   RAxMLRunner              <- .../pepr/tree/RAxMLRunner.java:64-152,162-213,320-336
   FastTreeRunner           <- .../pepr/tree/FastTreeRunner.java:38-135,142-199,235
   TreeComparison.runConsel <- .../pepr/tree/TreeComparison.java:812-885
+  compareAllvsAll, compareSlidingWindow, rollingComparison, getBranchDistance, getDiscrepantBranchDistance
+                           <- .../pepr/tree/TreeComparison.java:267-288, :241-265, :457-466, :607-747, :756-810 (pml_tree_compare)
+  BasicTree.removeTaxon, pruneToCommonTaxa
+                           <- .../pepr/tree/BasicTree.java:888-946, TreeComparison.java:83-128 (host text work, no device)
   NeighborJoiningRunner    <- .../pepr/tree/pipeline/PhylogeneticTreeBuilder.java:198-208 buildNeighborJoiningTree (method "nj")
   buildConcatenatedNeighborJoiningTree
                            <- .../pepr/tree/pipeline/PhylogenomicPipeline2.java:1279-1293 (the `-nj true` path: topology only)
@@ -370,6 +374,198 @@ class TreeComparison:
             lines.append("# %4d %4d %8.1f %6.3f %6.3f | %6.3f %6.3f %6.3f %6.3f |" % (
                 r["rank"][t], t + 1, r["obs"][t], r["au"][t], r["np"][t], r["bp"][t], r["pp"][t], r["kh"][t], r["sh"][t]))
         return lines
+
+
+# ---- TreeComparison's -rf / -tree_dist legs: every value comes from one pml_tree_compare call on the device ----
+def compareAllvsAll(trees, ctx=None, useLengths=True):
+    """TreeComparison.compareAllvsAll(TreeI[]) (:267-288) on Newick strings over one leaf set -> the dict of Context.tree_compare:
+    rf_legacy is the int[][] the Java returns, branch_dist / discrepant_dist the two values it prints per pair"""
+    return (ctx or default_context()).tree_compare(list(trees), use_lengths=useLengths)
+
+
+def compareSlidingWindow(trees, windowSize, ctx=None):
+    """TreeComparison.compareSlidingWindow (:241-265): for i >= windowSize the legacy RF of tree i against each of the windowSize
+    trees before it -> [(i, [(j, distance), ...], min, max, mean)] as the Java prints them (mean = sum / count in doubles)"""
+    rf = (ctx or default_context()).tree_compare(list(trees), window=windowSize, want=["rf_legacy"])["rf_legacy"]
+    out = []
+    for i in range(windowSize, len(trees)):
+        d = [(j, int(rf[i, j])) for j in range(i - windowSize, i)]
+        v = [x for _, x in d]
+        out.append((i, d, min(v), max(v), float(sum(v)) / len(v)))
+    return out
+
+
+def rollingComparison(trees, ctx=None):
+    """TreeComparison.rollingComparison (:457-466): r[i] = legacy RF between trees i + 1 and i"""
+    rf = (ctx or default_context()).tree_compare(list(trees), window=1, want=["rf_legacy"])["rf_legacy"]
+    return [int(rf[i + 1, i]) for i in range(len(trees) - 1)]
+
+
+def getBranchDistance(tree1, tree2, ctx=None, useLengths=True):
+    """TreeComparison.getBranchDistance (:607-747) of two Newick strings; tree1 is the Java's tree1"""
+    return float((ctx or default_context()).tree_compare_one(tree1, [tree2], use_lengths=useLengths, want=["branch_dist"])["branch_dist"][0])
+
+
+def getDiscrepantBranchDistance(tree1, tree2, ctx=None, useLengths=True):
+    """TreeComparison.getDiscrepantBranchDistance (:756-810)"""
+    return float((ctx or default_context()).tree_compare_one(tree1, [tree2], use_lengths=useLengths, want=["discrepant_dist"])["discrepant_dist"][0])
+
+
+def compressTaxonNameForComparison(name):
+    """TreeUtils.compressTaxonNameForComparison (TreeUtils.java:48-73)"""
+    import re
+    r = name
+    if re.fullmatch(r".*\.f.+", r, re.S):
+        r = r[:r.rindex(".")]
+    if r.endswith(".PATRIC"):
+        r = r[:r.rindex(".")]
+    return re.sub(r"[\._,\s]", "", r).lower()
+
+
+class BasicTree:
+    """The part of BasicTree that TreeComparison's pruning uses, for well-formed Newick text: the node arrays of
+    parseNewickTreeString (BasicTree.java:131-409: leaves in text order, then inner nodes in the order of their ')'; a branch
+    without a length has length 0.0; the text between ')' and ':' is the node's support string), populateChildPointers
+    (:411-448: children in ascending node index), removeTaxon (:888-946) and getTreeString (:450-520)."""
+    NO_PARENT = -1
+
+    def __init__(self, treeString):
+        s = treeString.strip()
+        if s.endswith(";"):
+            s = s[:-1]
+        self.leaves, inner = [], []            # inner: (children as ("l" | "i", index), length, support), in the order of ')'
+        leaf_len = []
+        pos = 0
+
+        def sub():
+            nonlocal pos
+            kids = []
+            if s[pos] == "(":
+                pos += 1
+                while True:
+                    kids.append(sub())
+                    if s[pos] == ",":
+                        pos += 1
+                        continue
+                    if s[pos] == ")":
+                        pos += 1
+                        break
+                    raise ValueError("expected , or ) at %d" % pos)
+            b = pos
+            while pos < len(s) and s[pos] not in ",():":
+                pos += 1
+            label = s[b:pos]
+            length = 0.0
+            if pos < len(s) and s[pos] == ":":
+                pos += 1
+                b = pos
+                while pos < len(s) and s[pos] not in ",()":
+                    pos += 1
+                length = float(s[b:pos])
+            if kids:
+                inner.append((kids, length, label or None))
+                return ("i", len(inner) - 1)
+            self.leaves.append(label)
+            leaf_len.append(length)
+            return ("l", len(self.leaves) - 1)
+
+        sub()
+        if pos != len(s):
+            raise ValueError("text after the tree at %d" % pos)
+        nl = len(self.leaves)
+        n = nl + len(inner)
+        self.nodeStrings = list(self.leaves) + [None] * len(inner)
+        self.parent = [self.NO_PARENT] * n
+        self.branchLengths = leaf_len + [x[1] for x in inner]
+        self.branchSupports = [None] * nl + [x[2] for x in inner]
+        for k, (kids, _, _) in enumerate(inner):
+            for kind, idx in kids:
+                self.parent[idx if kind == "l" else nl + idx] = nl + k
+        self.children = [[c for c in range(n) if self.parent[c] == v] for v in range(n)]      # ascending index (:438-447)
+
+    def getLeaves(self):
+        """the leaves still in the tree, in node order"""
+        top = self.getTopLevelNode()
+        out = []
+
+        def walk(v):
+            if not self.children[v]:
+                out.append(self.nodeStrings[v])
+            for c in self.children[v]:
+                walk(c)
+        if top >= 0:
+            walk(top)
+        return out
+
+    def removeTaxon(self, taxon):
+        idx = -1
+        for i, leaf in enumerate(self.leaves):                                  # :891-895: the LAST match
+            if taxon.lower() == leaf.lower() or compressTaxonNameForComparison(taxon) == compressTaxonNameForComparison(leaf):
+                idx = i
+        if idx < 0 or self.parent[idx] == self.NO_PARENT:                       # :897-903
+            return
+        parent = self.parent[idx]
+        self.children[parent].remove(idx)                                       # removeChildNode :815-829
+        self.parent[idx] = self.NO_PARENT
+        if len(self.children[parent]) == 1:                                     # :910-935
+            rest = self.children[parent][0]
+            if self.parent[parent] == self.NO_PARENT:
+                self.parent[rest] = self.NO_PARENT
+                self.children[parent] = []
+            else:
+                grand = self.parent[parent]
+                self.branchLengths[rest] += self.branchLengths[parent]
+                self.children[grand][self.children[grand].index(parent)] = rest
+                self.parent[rest] = grand
+
+    def getTopLevelNode(self):
+        r = -1
+        for i in range(len(self.parent)):                                       # :466-472: the last node without a parent that has children
+            if self.parent[i] == self.NO_PARENT and self.children[i]:
+                r = i
+        return r
+
+    def getTreeString(self, includeLengths=True, includeSupports=True):
+        top = self.getTopLevelNode()
+        if top < 0:
+            return None
+
+        def node(v):                                                            # getNodeString :480-520
+            kids = self.children[v]
+            if not kids:
+                return self.nodeStrings[v]
+            parts = []
+            for c in kids:
+                parts.append(node(c) + (":" + engine.format_double(self.branchLengths[c]) if includeLengths else ""))
+            r = ",".join(parts)
+            if len(kids) > 1:
+                r = "(" + r + ")"
+            if includeSupports and self.branchSupports[v] is not None:
+                r += self.branchSupports[v]
+            return r
+        return node(top) + ";"
+
+
+def pruneToCommonTaxa(treeStrings, outgroupTaxa=(), useLengths=True):
+    """What TreeComparison.main does to its trees before it compares them: every outgroup taxon (sorted, :88) is removed from
+    every tree (:89-96), then every taxon that is not in all trees (:101-127); after each removal the tree is rebuilt from its
+    own text, as the Java rebuilds it (:94, :124) -> (the pruned Newick strings, [(tree index, removed taxon)])"""
+    trees = [BasicTree(t) for t in treeStrings]
+    removed = []
+    for taxon in sorted(outgroupTaxa):
+        for j in range(len(trees)):
+            trees[j].removeTaxon(taxon)
+            trees[j] = BasicTree(trees[j].getTreeString(useLengths, True))
+    common = set(trees[0].getLeaves()) if trees else set()
+    for t in trees[1:]:
+        common &= set(t.getLeaves())
+    for i in range(len(trees)):
+        for taxon in trees[i].getLeaves():                                      # :118: the leaves before any removal
+            if taxon not in common:
+                removed.append((i, taxon))
+                trees[i].removeTaxon(taxon)
+                trees[i] = BasicTree(trees[i].getTreeString(useLengths, True))
+    return [t.getTreeString(useLengths, True) for t in trees], removed
 
 
 class PhylogeneticTreeBuilder:
