@@ -667,6 +667,52 @@ int  pml_debug_column_splits(pml_ctx *ctx, const pml_alignment *gene, int nunion
 /* the kept splits that k_splitcost holds in LDS at a time (tests size a case beyond it) */
 int  pml_congruence_ktile(void);
 
+/* The reference's `-uniform_trim` (HandyConstants.java:26; PhylogenomicPipeline2.getAlignment :788-795 runs it on every gene before
+ * filterForCongruence sees them) and MSATrimmer's two sibling filters, on the device (trim.hip).  Bytes are compared by identity
+ * (no alphabet: 'a' and 'A' differ); n is the gene's OWN number of rows, nothing here involves a union of taxa, and n has no
+ * bound.  For a column let seen1 = the set of bytes that occur, seen2 = the set of bytes that occur at least twice, shown = the
+ * number of rows whose byte is neither '-' nor '?'.
+ *   PML_TRIM_UNIFORM      trimUniformColumns (MSATrimmer.java:205-253): a column is kept iff getMinimumStepsPerSite
+ *            (SequenceAlignment.java:673-682) is non-zero, i.e. iff it has more than one distinct Bipartition
+ *            (getBipartitionsForAlignmentColumn :808-902).  With classes = |seen1 \ {'-','?'}|: kept iff classes >= 3, or classes == 2
+ *            and shown < n.  Two classes that cover all n rows normalise to ONE bipartition (Bipartition.equals :292-303 compares the
+ *            sides only), so the gap-free column AAAC or AACC is dropped while AAC- is kept: not what the name suggests, but
+ *            the Java.  A column of nothing but '-' and '?' makes the Java dereference null; the library refuses it with PML_EPARSE
+ *            and names gene and column (a deliberate difference).
+ *   PML_TRIM_GAP_UNIFORM  trimUniformativeColumns (:141-203): only '-' is skipped, '?' is a character like any other; kept iff at
+ *            least two distinct bytes other than '-' occur.  An all-'-' column is uniform and dropped.
+ *   PML_TRIM_TOPOLOGICAL  trimTopologicallyUninformativeColumns (:264-351): only '-' is skipped; kept iff at least two distinct
+ *            bytes other than '-' each occur at least twice, |seen2 \ {'-'}| >= 2.  All-'-' columns are dropped.  (Its
+ *            uninformativeCount is a debug print and not part of the contract.)
+ * In every mode the kept columns keep their order, rows and names are untouched, a gene may end with 0 columns, and gap_or_missing
+ * is the numerator of getProportionGapOrMissing (SequenceAlignment.java:1074-1092): the '-' and '?' cells of the UNTRIMMED gene.
+ * pml_trim_columns works through the genes in sub-batches that fit the HBM budget (0.85 of free HBM, or PML_HBM_BUDGET_MB): input,
+ * output and flags of a sub-batch are resident together; a single gene that does not fit is PML_ENOMEM with the size. */
+enum { PML_TRIM_UNIFORM = 0, PML_TRIM_GAP_UNIFORM = 1, PML_TRIM_TOPOLOGICAL = 2 };
+typedef struct {
+    int ngenes;
+    int *ntax, *ncols, *nkept;        /* [G]: rows, columns before, columns kept */
+    int **kept_cols;                  /* [G][nkept] ascending column indices */
+    char ***rows;                     /* [G][ntax] the trimmed rows in input order, 0-terminated, owned by the result */
+    long long *gap_or_missing;        /* [G] */
+} pml_trim_result;
+int  pml_trim_columns(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int mode, pml_trim_result *result);
+void pml_trim_result_free(pml_trim_result *result);
+/* `-uniform_trim -congruence_filter` in one resident call: the genes are uploaded once, trimmed in HBM, and the congruence stage
+ * runs on the trimmed device matrices.  Equals pml_trim_columns followed by pml_congruence_filter on the returned text, field for
+ * field.  A gene trimmed to 0 columns is PML_EPARSE and names the gene (the Java divides by zero there).  The union of taxa is the
+ * congruence filter's (at most 512); trim_result and congruence_result may each be NULL. */
+int  pml_trim_congruence_filter(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int mode, double trim_percent, int *keep_out,
+                                pml_trim_result *trim_result, pml_congruence_result *congruence_result);
+/* test door of k_colclass: one byte per column as the kernel wrote it: bit 0, bit 1, bit 2 = kept under PML_TRIM_UNIFORM,
+ * PML_TRIM_GAP_UNIFORM, PML_TRIM_TOPOLOGICAL; bit 3 = only '-' / '?'.  flags_out: gene->nsites bytes */
+int  pml_debug_column_flags(pml_ctx *ctx, const pml_alignment *gene, unsigned char *flags_out);
+/* host-only, needs no context: the same bytes from the same decision function (csrc/trim.hpp) */
+int  pml_trim_column_flags_host(const pml_alignment *gene, unsigned char *flags_out);
+/* k_colclass and k_colgather launches on this context so far and, with cfg.profile = 1, summed HIP-event times in ms:
+ * total_ms[0] = k_colclass, [1] = k_colgather, [2] = the host-to-device copies of the genes' bytes.  Never reset. */
+int  pml_trim_stats(pml_ctx *ctx, long long *class_launches, long long *gather_launches, double *total_ms /* [3] */);
+
 /* TreeComparison's `-rf` and `-tree_dist` legs (TreeComparison.java:48-50, compareAllvsAll :267-288) for a whole set of trees:
  * every pair (i, j), i < j, tree 1 = i, on the device (treecmp.hip).  The trees are given as Newick text and must all have the
  * same leaf labels (PML_EINVAL otherwise; at most 512 leaves, at least 3).

@@ -31,6 +31,8 @@ SYMBOLS = [
     "pml_jackknife3", "pml_fitch_stats", "pml_debug_fitch_tips",
     "pml_tree_compare", "pml_tree_compare_one", "pml_tree_compare_result_free", "pml_debug_tree_splits", "pml_tree_splits_free",
     "pml_debug_tree_pair_sums",
+    "pml_trim_columns", "pml_trim_result_free", "pml_trim_congruence_filter", "pml_debug_column_flags", "pml_trim_column_flags_host",
+    "pml_trim_stats",
 ]
 
 
@@ -142,6 +144,12 @@ class CongruenceResult(C.Structure):
                 ("cost_sum", _lp), ("mean_cost", _lp), ("nsplits", C.POINTER(C.c_int)), ("cutoff", C.c_int), ("nkept", C.c_longlong),
                 ("kept_words", C.POINTER(C.c_ulonglong)), ("kept_count", _lp), ("kept_cost", _lp),
                 ("nrecords", C.c_longlong), ("ndistinct", C.c_longlong)]
+
+
+class TrimResult(C.Structure):
+    _ip = C.POINTER(C.c_int)
+    _fields_ = [("ngenes", C.c_int), ("ntax", _ip), ("ncols", _ip), ("nkept", _ip), ("kept_cols", C.POINTER(_ip)),
+                ("rows", C.POINTER(C.POINTER(C.c_void_p))), ("gap_or_missing", C.POINTER(C.c_longlong))]
 
 
 _lib = None
@@ -270,5 +278,13 @@ def load():
     L.pml_tree_splits_free.argtypes = [C.POINTER(TreeSplits)]
     L.pml_tree_splits_free.restype = None
     L.pml_debug_tree_pair_sums.argtypes = [vp, C.c_int, cpp, C.c_int, C.c_int, ip, lp, dp]
+    trp2 = C.POINTER(TrimResult)
+    L.pml_trim_columns.argtypes = [vp, C.c_int, ap, C.c_int, trp2]
+    L.pml_trim_result_free.argtypes = [trp2]
+    L.pml_trim_result_free.restype = None
+    L.pml_trim_congruence_filter.argtypes = [vp, C.c_int, ap, C.c_int, C.c_double, ip, trp2, crp]
+    L.pml_debug_column_flags.argtypes = [vp, ap, C.POINTER(C.c_ubyte)]
+    L.pml_trim_column_flags_host.argtypes = [ap, C.POINTER(C.c_ubyte)]
+    L.pml_trim_stats.argtypes = [vp, lp, lp, dp]
     _lib = L
     return L

@@ -12,6 +12,7 @@
 #include "../../include/peprml.h"
 #include "api_types.hpp"
 #include "congruence.hpp"
+#include "congruence_dev.hpp"
 
 using namespace pml;
 
@@ -26,6 +27,8 @@ struct Congruence {
     Ctx *ctx = nullptr;
     std::vector<std::string> names; int n = 0, W = 1, ngenes = 0;
     std::vector<int> ncols;
+    std::vector<std::vector<std::pair<int, int>>> order;     // per gene: (union index, row) ascending
+    std::vector<char> host;                                  // stage 1's staging block, until the first sync
     long long total_cols = 0, nrec = 0;
     size_t budget = 0, used = 0;
     char *d_in = nullptr, *d_rec = nullptr, *d_k = nullptr;
@@ -45,8 +48,9 @@ struct Congruence {
         return PML_OK;
     }
 
-    // rules 1 and 2: every column's splits as records in HBM.  given: the union to use (the debug hook), else the genes' own
-    int extract(int ng, const pml_alignment *genes, const std::vector<std::string> *given) {
+    // the checks of the genes, the union (given: the one to use, the debug hook; else the genes' own) and every gene's rows in
+    // ascending union index; a repeated name: its last row, as pml_concatenate
+    int plan(int ng, const pml_alignment *genes, const std::vector<std::string> *given) {
         ngenes = ng;
         for (int g = 0; g < ng; ++g) {
             const pml_alignment &A = genes[g];
@@ -66,11 +70,7 @@ struct Congruence {
         W = cg_words(n);
         std::unordered_map<std::string, int> index;
         for (int i = 0; i < n; ++i) index[names[i]] = i;
-        // a gene's rows in ascending union index; a repeated name: its last row, as pml_concatenate
-        std::vector<std::vector<std::pair<int, int>>> order((size_t)ng);
-        std::vector<size_t> o_map((size_t)ng), o_bytes((size_t)ng), ld((size_t)ng);
-        ncols.resize((size_t)ng);
-        long long tiles = 0;
+        order.assign((size_t)ng, {});
         for (int g = 0; g < ng; ++g) {
             std::vector<int> row_of((size_t)n, -1);
             for (int i = 0; i < genes[g].ntax; ++i) {
@@ -81,7 +81,18 @@ struct Congruence {
                 row_of[(size_t)it->second] = i;
             }
             for (int u = 0; u < n; ++u) if (row_of[(size_t)u] >= 0) order[(size_t)g].push_back({u, row_of[(size_t)u]});
-            ncols[g] = genes[g].nsites; total_cols += ncols[g]; tiles += (ncols[g] + CG_COLS - 1) / CG_COLS;
+        }
+        return PML_OK;
+    }
+
+    // stage 1 in HBM.  genes: their text is uploaded in the CgGene layout; resident: they are there already (col_base is set here)
+    int stage(const pml_alignment *genes, const CgGene *resident) {
+        const int ng = ngenes;
+        std::vector<size_t> o_map((size_t)ng), o_bytes((size_t)ng), ld((size_t)ng);
+        ncols.resize((size_t)ng);
+        long long tiles = 0;
+        for (int g = 0; g < ng; ++g) {
+            ncols[g] = genes ? genes[g].nsites : resident[g].ncols; total_cols += ncols[g]; tiles += (ncols[g] + CG_COLS - 1) / CG_COLS;
             max_ntax = std::max(max_ntax, (int)order[(size_t)g].size());
             cells += (double)order[(size_t)g].size() * ncols[g];
         }
@@ -90,7 +101,7 @@ struct Congruence {
         size_t off = align_up((size_t)ng * sizeof(CgGene), 256);
         o_tiles = off; off += align_up((size_t)ntiles * sizeof(int), 256);
         o_first = off; off += align_up((size_t)ng * sizeof(int), 256);
-        for (int g = 0; g < ng; ++g) {
+        for (int g = 0; genes && g < ng; ++g) {
             const size_t nt = order[(size_t)g].size();
             ld[g] = align_up((size_t)ncols[g], 16);
             o_map[g] = off; off += align_up(nt * sizeof(uint16_t), 256);
@@ -104,26 +115,38 @@ struct Congruence {
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 40;
         budget = (size_t)(0.85 * (double)free_b);
         if (const char *e = std::getenv("PML_HBM_BUDGET_MB")) budget = (size_t)std::atoll(e) << 20;
+        else budget += used;                               // what a caller holds for this call was free before it took it
         if (int rc = fits(off, "the genes' bytes")) return rc;
         CGCHK(hipMalloc((void **)&d_in, off));
-        std::vector<char> host(in_bytes, '?');
+        host.assign(in_bytes, '?');
         {
             int *tile_gene = (int *)(host.data() + o_tiles), *tile_first = (int *)(host.data() + o_first);
             long long col_base = 0; int t = 0;
             for (int g = 0; g < ng; ++g) {
                 const auto &ord = order[(size_t)g];
-                uint16_t *map = (uint16_t *)(host.data() + o_map[g]);
-                for (size_t r = 0; r < ord.size(); ++r) {
-                    map[r] = (uint16_t)ord[r].first;
-                    std::memcpy(host.data() + o_bytes[g] + r * ld[g], genes[g].rows[ord[r].second], (size_t)ncols[g]);
+                if (genes) {
+                    uint16_t *map = (uint16_t *)(host.data() + o_map[g]);
+                    for (size_t r = 0; r < ord.size(); ++r) {
+                        map[r] = (uint16_t)ord[r].first;
+                        std::memcpy(host.data() + o_bytes[g] + r * ld[g], genes[g].rows[ord[r].second], (size_t)ncols[g]);
+                    }
+                    ((CgGene *)host.data())[g] = CgGene{(const uint8_t *)(d_in + o_bytes[g]), (const uint16_t *)(d_in + o_map[g]), (int)ord.size(), ncols[g], (int)ld[g], col_base};
+                } else {
+                    CgGene rg = resident[g]; rg.col_base = col_base;
+                    ((CgGene *)host.data())[g] = rg;
                 }
-                ((CgGene *)host.data())[g] = CgGene{(const uint8_t *)(d_in + o_bytes[g]), (const uint16_t *)(d_in + o_map[g]), (int)ord.size(), ncols[g], (int)ld[g], col_base};
                 tile_first[g] = t;
                 for (int k = 0; k < (ncols[g] + CG_COLS - 1) / CG_COLS; ++k) tile_gene[t++] = g;
                 col_base += ncols[g];
             }
         }
         CGCHK(hipMemcpyAsync(d_in, host.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        return PML_OK;
+    }
+
+    // rules 1 and 2: every column's splits as records in HBM
+    int records() {
+        const int ng = ngenes;
         ctx->tic(K_COLSPLIT, cells);
         launch_colsplits((const CgGene *)d_in, (const int *)(d_in + o_tiles), (const int *)(d_in + o_first), ntiles, max_ntax, n, (int *)(d_in + o_nsplit),
                          nullptr, nullptr, nullptr, nullptr, ctx->stream);
@@ -133,12 +156,13 @@ struct Congruence {
         CGCHK(hipMemcpyAsync(nsplit.data(), d_in + o_nsplit, nsplit.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         if (ctx->sync(ctx->stream)) return PML_EDEVICE;
         ctx->resolve_events();
+        std::vector<char>().swap(host);
         std::vector<long long> rec_off((size_t)total_cols);
         for (long long c = 0; c < total_cols; ++c) { rec_off[(size_t)c] = nrec; nrec += nsplit[(size_t)c]; }
         if (nrec > INT_MAX - 1) return ctx->fail(PML_ENOMEM, "the call has " + std::to_string(nrec) + " split records: at most 2^31 - 2 fit one call");
         if (nrec == 0) return PML_OK;
         cap = pow2_at_least(2ull * (unsigned long long)nrec);
-        off = 0;
+        size_t off = 0;
         auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; };
         take((size_t)nrec * W * sizeof(unsigned long long));
         o_col = take((size_t)nrec * sizeof(long long)); o_gene = take((size_t)nrec * sizeof(int)); o_id = take((size_t)nrec * sizeof(int));
@@ -156,13 +180,19 @@ struct Congruence {
                          (const long long *)(d_in + o_off), (unsigned long long *)d_rec, (int *)(d_rec + o_gene), (long long *)(d_rec + o_col), ctx->stream);
         ctx->toc();
         CGCHK(hipGetLastError());
-        if (ctx->sync(ctx->stream)) return PML_EDEVICE;            // rec_off and the staging vector go out of scope
+        if (ctx->sync(ctx->stream)) return PML_EDEVICE;            // rec_off goes out of scope
         ctx->resolve_events();
         return PML_OK;
     }
 
+    int extract(int ng, const pml_alignment *genes, const std::vector<std::string> *given) {
+        if (int rc = plan(ng, genes, given)) return rc;
+        if (int rc = stage(genes, nullptr)) return rc;
+        return records();
+    }
+
     // rules 3 to 6 on the records of extract()
-    int charge(const pml_alignment *genes, unsigned long long hash_mask, pml_congruence_result *res) {
+    int charge(unsigned long long hash_mask, pml_congruence_result *res) {
         std::vector<long long> cost_sum((size_t)ngenes, 0); std::vector<int> ndist_g((size_t)ngenes, 0);
         std::vector<unsigned long long> kwords; std::vector<int> kcount; std::vector<long long> kcost;
         int cutoff = 0; size_t D = 0;
@@ -244,7 +274,7 @@ struct Congruence {
             if (res->names[i]) std::memcpy(res->names[i], names[(size_t)i].c_str(), names[(size_t)i].size() + 1); else ok = false;
         }
         if (!ok) { pml_congruence_result_free(res); return ctx->fail(PML_ENOMEM, "host allocation failed"); }
-        for (size_t g = 0; g < G; ++g) { res->cost_sum[g] = cost_sum[g]; res->mean_cost[g] = cost_sum[g] / genes[g].nsites; res->nsplits[g] = ndist_g[g]; }
+        for (size_t g = 0; g < G; ++g) { res->cost_sum[g] = cost_sum[g]; res->mean_cost[g] = cost_sum[g] / ncols[g]; res->nsplits[g] = ndist_g[g]; }
         std::copy(kwords.begin(), kwords.end(), res->kept_words);
         for (size_t j = 0; j < K; ++j) { res->kept_count[j] = kcount[j]; res->kept_cost[j] = kcost[j]; }
         return PML_OK;
@@ -257,11 +287,32 @@ int costs_locked(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml
     try {
         Congruence cg; cg.ctx = &ctx->c;
         if (int rc = cg.extract(ngenes, genes, nullptr)) return rc;
-        return cg.charge(genes, opts && opts->use_hash_mask ? opts->hash_mask : ~0ull, result);
+        return cg.charge(opts && opts->use_hash_mask ? opts->hash_mask : ~0ull, result);
     } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
     catch (const std::exception &e) { return ctx->c.fail(PML_EINVAL, e.what()); }
 }
 }  // namespace
+
+int pml::cg_plan(Ctx *ctx, int ngenes, const pml_alignment *genes, CgPlan &plan) {
+    Congruence cg; cg.ctx = ctx;
+    if (int rc = cg.plan(ngenes, genes, nullptr)) return rc;
+    plan.names.swap(cg.names); plan.order.swap(cg.order);
+    return PML_OK;
+}
+
+int pml::cg_costs_resident(pml_ctx *ctx, const CgPlan &plan, const std::vector<CgGene> &genes, size_t resident_bytes, pml_congruence_result *result) {
+    try {
+        Congruence cg; cg.ctx = &ctx->c;
+        cg.ngenes = (int)genes.size(); cg.names = plan.names; cg.n = (int)plan.names.size(); cg.W = cg_words(cg.n); cg.order = plan.order;
+        cg.used = resident_bytes;
+        for (size_t g = 0; g < genes.size(); ++g)
+            if (genes[g].ncols <= 0) return ctx->c.fail(PML_EPARSE, "gene " + std::to_string(g) + " has no columns");
+        if (int rc = cg.stage(nullptr, genes.data())) return rc;
+        if (int rc = cg.records()) return rc;
+        return cg.charge(~0ull, result);
+    } catch (const std::bad_alloc &) { return ctx->c.fail(PML_ENOMEM, "host allocation failed"); }
+    catch (const std::exception &e) { return ctx->c.fail(PML_EINVAL, e.what()); }
+}
 
 extern "C" void pml_congruence_result_free(pml_congruence_result *r) {
     if (!r) return;

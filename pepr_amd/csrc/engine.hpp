@@ -46,6 +46,7 @@ struct Ctx {
     long long pairsum_launches = 0; double pairsum_ms = 0;      // k_pairscore_sum launches and (profile mode) their HIP-event time (pml_pairscore_sum_stats)
     long long newton_giveups = 0, newton_reissued = 0, newton_seq_launches = 0;   // k_newton fallback statistics (pml_newton_fallbacks)
     long long fitch_tips_launches = 0, fitch_launches = 0;      // k_fitch_tips and k_fitch launches (pml_fitch_stats)
+    long long colclass_launches = 0, colgather_launches = 0; double trim_ms[3] = {0, 0, 0};   // pml_trim_stats: k_colclass, k_colgather, the uploads
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;
     std::vector<hipEvent_t> pool;

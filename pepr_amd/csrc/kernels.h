@@ -229,6 +229,18 @@ void launch_splitcost(const unsigned long long *rec, const int *dist, long long 
 void launch_genecost(const int *rec_gene, const int *split_id, long long nrec, const long long *cost_rec, unsigned long long *keys,
                      unsigned long long cap, unsigned long long hash_mask, long long *cost_sum, int *ndistinct, int *err, hipStream_t s);
 
+// Column trimming (trim.hip, rules in trim.hpp): MSATrimmer's three filters in front of the congruence filter.  Genes come in
+// the CgGene layout (map is not read; ntax = the gene's own rows, any number of them).
+// k_colclass: one workgroup per entry of tile_gene (TRIM_COLS columns of that gene, tile_first[gene] = its first tile), thread =
+// one column: flags[col_base + column] = the column's TRIM_* byte; gap_or_missing[gene] += its '-' and '?' cells (zeroed by the caller)
+void launch_colclass(const CgGene *genes, const int *tile_gene, const int *tile_first, int ntiles, uint8_t *flags, long long *gap_or_missing, hipStream_t s);
+// k_colgather: out[r][j] = in[r][src_col[j]] for j < nkept, 0 for nkept <= j < ld_out; ld_out = nkept rounded up to 16, src_col holds
+// ld_out entries (16-byte aligned, the padding ones anything), out is 16-byte aligned.  One workgroup per tile: TRIM_CHUNKS
+// 16-byte chunks of TRIM_ROWS rows of one gene, from chunk0 and row0
+struct TgGene { const uint8_t *in; uint8_t *out; const int *src_col; int ntax, nkept, ld_in, ld_out; };
+struct TgTile { int gene, chunk0, row0, pad; };
+void launch_colgather(const TgGene *genes, const TgTile *tiles, int ntiles, hipStream_t s);
+
 // Tree-set comparison (treecmp.hip): the split records of T trees, compact: tree t owns entries off[t] .. off[t] + cnt[t] - 1 of
 // every array, its first nreal[t] are TreeBranches in the Java's order (treecmp.hpp).  id = interned split id, ln / lr =
 // length over the tree's maximum / the length itself, flags = TC_*; sid / sidx = the tree's (id, record index) pairs sorted

@@ -17,6 +17,7 @@ PI_GTR = 3             # PROTGAMMAGTR: exchangeabilities estimated per gene by t
 NJ_DISTANCE, NJ_SIMILARITY = 0, 1      # pml_nj_from_matrix matrix types (TreeBuilder.DISTANCE / SIMILARITY)
 NJ_TREE, NJ_TOPOLOGY = 0, 1            # getNJTreeString (lengths) / getNJTopology (the `-nj true` path)
 TREE_ML, TREE_PARSIMONY, TREE_PARSIMONY_BL = 0, 1, 2      # pml_jackknife3 tree-building methods (PML_TREE_*)
+TRIM_UNIFORM, TRIM_GAP_UNIFORM, TRIM_TOPOLOGICAL = 0, 1, 2     # pml_trim_columns modes (PML_TRIM_*): MSATrimmer's three filters
 EINVAL = -1
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
@@ -40,6 +41,11 @@ def _aln_struct(names, rows, keep):
     ra = (C.c_char_p * n)(*[s.encode() if isinstance(s, str) else s for s in rows])
     keep.extend([na, ra])
     return _lib.Alignment(n, L, na, ra)
+
+
+def _raw_aln_struct(names, rows, keep):
+    """as _aln_struct for the calls that compare bytes by identity: a str row is its latin-1 bytes (one byte per character)"""
+    return _aln_struct(names, [r.encode("latin-1") if isinstance(r, str) else r for r in rows], keep)
 
 
 def _model(ncat=4, alpha=1.0, pi_mode=PI_RAXML_3DP):
@@ -576,6 +582,67 @@ class Context:
         out.update(congruence_select(out["mean_cost"], trim_percent))          # idx and max_cost
         out["keep"] = [bool(f) for f in flags]
         return out
+
+    # ---- the reference's `-uniform_trim` and MSATrimmer's sibling filters (include/peprml.h pml_trim_columns) ----
+    def _trim_result(self, res, genes):
+        out = []
+        for g in range(res.ngenes):
+            nk = res.nkept[g]
+            rows = [C.string_at(res.rows[g][i], nk) for i in range(res.ntax[g])]
+            if genes[g][1] and isinstance(genes[g][1][0], str):
+                rows = [r.decode("latin-1") for r in rows]
+            out.append({"names": list(genes[g][0]), "rows": rows, "ncols": res.ncols[g], "nkept": nk,
+                        "kept_cols": [res.kept_cols[g][j] for j in range(nk)], "gap_or_missing": res.gap_or_missing[g]})
+        return out
+
+    def trim_columns(self, genes, mode=TRIM_UNIFORM):
+        """MSATrimmer's column filters on the device -> per gene {"names", "rows" (the trimmed rows, str or bytes as given),
+        "ncols", "nkept", "kept_cols", "gap_or_missing"}.  mode: TRIM_UNIFORM (what -uniform_trim runs), TRIM_GAP_UNIFORM,
+        TRIM_TOPOLOGICAL.  Bytes are compared by identity; a str row stands for its latin-1 bytes."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_raw_aln_struct(g[0], g[1], keep) for g in genes])
+        res = _lib.TrimResult()
+        self._check(self.L.pml_trim_columns(self.ptr, n, alns, int(mode), C.byref(res)))
+        try:
+            return self._trim_result(res, genes)
+        finally:
+            self.L.pml_trim_result_free(C.byref(res))
+
+    def trim_congruence_filter(self, genes, mode=TRIM_UNIFORM, trim_percent=0.1):
+        """`-uniform_trim -congruence_filter` in one resident call (one upload): -> congruence_filter's dict on the trimmed genes,
+        plus "trimmed": trim_columns' list"""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_raw_aln_struct(g[0], g[1], keep) for g in genes])
+        tres, res = _lib.TrimResult(), _lib.CongruenceResult()
+        flags = (C.c_int * n)()
+        self._check(self.L.pml_trim_congruence_filter(self.ptr, n, alns, int(mode), float(trim_percent), flags, C.byref(tres), C.byref(res)))
+        try:
+            out = self._congruence_result(res)
+            out["trimmed"] = self._trim_result(tres, genes)
+        finally:
+            self.L.pml_congruence_result_free(C.byref(res))
+            self.L.pml_trim_result_free(C.byref(tres))
+        out.update(congruence_select(out["mean_cost"], trim_percent))          # idx and max_cost
+        out["keep"] = [bool(f) for f in flags]
+        return out
+
+    def debug_column_flags(self, gene):
+        """Test door of k_colclass: one byte per column as the kernel wrote it (bits 0 to 2: kept under the three modes; bit 3:
+        only '-' / '?') -> uint8 array"""
+        keep = []
+        a = _raw_aln_struct(gene[0], gene[1], keep)
+        out = np.zeros(max(a.nsites, 1), dtype=np.uint8)
+        self._check(self.L.pml_debug_column_flags(self.ptr, C.byref(a), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out[:a.nsites]
+
+    def trim_stats(self):
+        """k_colclass / k_colgather launches on this context so far and (profile mode) the summed HIP-event times in ms of the
+        two kernels and of the host-to-device copies of the genes"""
+        a, b, ms = C.c_longlong(), C.c_longlong(), (C.c_double * 3)()
+        self._check(self.L.pml_trim_stats(self.ptr, C.byref(a), C.byref(b), ms))
+        return {"class_launches": a.value, "gather_launches": b.value, "class_ms": ms[0], "gather_ms": ms[1], "upload_ms": ms[2]}
 
     # ---- TreeComparison's -rf / -tree_dist legs for a set of trees (include/peprml.h pml_tree_compare) ----
     TREE_COMPARE_ARRAYS = (("rf_legacy", 1, np.int32), ("rf_bipartition", 2, np.int32), ("rf_splits", 4, np.int32),
@@ -1156,6 +1223,17 @@ def congruence_select(mean_costs, trim_percent=0.1):
     if rc:
         raise PmlError(rc, "trim_percent %r with %d genes" % (trim_percent, n))
     return {"keep": [bool(k) for k in keep], "idx": idx.value, "max_cost": mx.value}
+
+
+def trim_column_flags_host(gene):
+    """pml_trim_column_flags_host: Context.debug_column_flags' bytes from the same decision function on the host (no device)"""
+    keep = []
+    a = _raw_aln_struct(gene[0], gene[1], keep)
+    out = np.zeros(max(a.nsites, 1), dtype=np.uint8)
+    rc = _lib.load().pml_trim_column_flags_host(C.byref(a), out.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    if rc:
+        raise PmlError(rc)
+    return out[:a.nsites]
 
 
 def congruence_ktile():

@@ -44,9 +44,16 @@ def default_context():
 class SequenceAlignment:
     """Minimal stand-in for .../pepr/alignment/SequenceAlignment.java: taxa + aligned char rows."""
 
-    def __init__(self, taxa, rows):
+    def __init__(self, taxa, rows, name=None):
         self.taxa = list(taxa)
         self.rows = list(rows)
+        self.name = name
+
+    def getName(self):
+        return self.name
+
+    def setName(self, name):
+        self.name = name
 
     def getTaxa(self):
         return self.taxa
@@ -343,6 +350,31 @@ def filterForCongruence(genes, percentileToRemove=0.1, ctx=None):
     pairs = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
     keep = ctx.congruence_filter(pairs, percentileToRemove)["keep"]
     return [g for g, k in zip(genes, keep) if k]
+
+
+class MSATrimmer:
+    """.../pepr/alignment/MSATrimmer.java's three column filters (:141-203, :205-253, :264-351) on the device
+    (Context.trim_columns; the rules are in include/peprml.h).  Each returns a new SequenceAlignment with the same taxa.  The
+    first two append "_ui" to the alignment's name (:197, :247: the Java concatenates, so a null name reads "null_ui"); the third
+    sets none.  Gblocks (trim) is not mirrored."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+
+    def _trim(self, alignment, mode, suffix):
+        ctx = self.ctx or default_context()
+        t = ctx.trim_columns([alignment.as_gene()], mode)[0]
+        name = alignment.getName()
+        return SequenceAlignment(alignment.getTaxa(), t["rows"], None if suffix is None else ("null" if name is None else name) + suffix)
+
+    def trimUniformativeColumns(self, alignment):
+        return self._trim(alignment, engine.TRIM_GAP_UNIFORM, "_ui")
+
+    def trimUniformColumns(self, alignment):
+        return self._trim(alignment, engine.TRIM_UNIFORM, "_ui")
+
+    def trimTopologicallyUninformativeColumns(self, alignment):
+        return self._trim(alignment, engine.TRIM_TOPOLOGICAL, None)
 
 
 class TreeComparison:

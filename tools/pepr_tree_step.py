@@ -9,7 +9,7 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
                          [--full-tree-method ml|parsimony|parsimony_bl|nj] [--support-tree-method ml|FastTree|parsimony|nj]
-                         [-congruence_filter] [-trim_percent 0.1]
+                         [-uniform_trim] [-congruence_filter] [-trim_percent 0.1]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
                   PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
@@ -28,6 +28,11 @@ usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-se
                   genes are filtered as PhylogenomicPipeline2.filterForCongruence filters them (column bipartition costs, the
                   genes of the highest mean cost go; P of 1.0 or more is a percentage).  Prints the reference's two messages and
                   writes <run>.congruence.tsv: file, columns, cost_sum, mean_cost, kept -- one row per gene
+-uniform_trim     PEPR's flag of the same name (HandyConstants.java:26): every gene goes through MSATrimmer.trimUniformColumns first,
+                  as getAlignment (PhylogenomicPipeline2.java:788-795) precedes filterForCongruence; the rule is in
+                  include/peprml.h (PML_TRIM_UNIFORM).  Writes <run>.trim.tsv: file, columns, kept -- one row per gene; a gene trimmed
+                  to 0 columns is dropped with a message.  With -congruence_filter the genes are uploaded once and trimmed and
+                  filtered in one call (pml_trim_congruence_filter)
 Without these flags the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
 """
 import glob
@@ -73,8 +78,30 @@ def main(argv):
     genes = [g for g in genes if len(g[0]) >= 3]
     reps = int(args.get("support_reps", 100))
     ctx = engine.Context(int(args.get("device", 0)))
-    if args.get("congruence_filter", "false").lower() == "true":
-        r = ctx.congruence_filter(genes, float(args.get("trim_percent", 0.1)))
+    filtering = args.get("congruence_filter", "false").lower() == "true"
+    r = None
+    if args.get("uniform_trim", "false").lower() == "true":
+        trimmed = None
+        if filtering:                           # one upload: trimmed in HBM, the congruence stage runs on the trimmed matrices
+            try:
+                r = ctx.trim_congruence_filter(genes, engine.TRIM_UNIFORM, float(args.get("trim_percent", 0.1)))
+                trimmed = r["trimmed"]
+            except engine.PmlError as e:        # a gene trimmed to nothing: it is dropped below and the two steps run one after the other
+                if e.code != -2 or "no columns left" not in str(e):
+                    raise
+        if trimmed is None:
+            trimmed = ctx.trim_columns(genes, engine.TRIM_UNIFORM)
+        with open(args["run_name"] + ".trim.tsv", "w") as f:
+            f.write("file\tcolumns\tkept\n")
+            for name, t in zip(files, trimmed):
+                f.write("%s\t%d\t%d\n" % (os.path.basename(name), t["ncols"], t["nkept"]))
+                if not t["nkept"]:
+                    print("dropping set %s: no column left after -uniform_trim" % os.path.basename(name))
+        files = [f for f, t in zip(files, trimmed) if t["nkept"]]
+        genes = [(t["names"], t["rows"]) for t in trimmed if t["nkept"]]
+    if filtering:
+        if r is None:
+            r = ctx.congruence_filter(genes, float(args.get("trim_percent", 0.1)))
         with open(args["run_name"] + ".congruence.tsv", "w") as f:
             f.write("file\tcolumns\tcost_sum\tmean_cost\tkept\n")
             for name, g, cs, mc, k in zip(files, genes, r["cost_sum"], r["mean_cost"], r["keep"]):
