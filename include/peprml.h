@@ -713,6 +713,72 @@ int  pml_trim_column_flags_host(const pml_alignment *gene, unsigned char *flags_
  * total_ms[0] = k_colclass, [1] = k_colgather, [2] = the host-to-device copies of the genes' bytes.  Never reset. */
 int  pml_trim_stats(pml_ctx *ctx, long long *class_launches, long long *gather_launches, double *total_ms /* [3] */);
 
+/* The gene homoplasy test of ConcatenatedSequenceAlignment.java:65-425: per-column parsimony steps of the concatenation on a tree,
+ * the least steps a column can take, per-gene totals, and for every gene a randomisation threshold (genesteps.hip).  In the
+ * reference this is dead code: its one input, setStepsPerSite (SequenceAlignment.java:1033), has no caller, because neither RAxML
+ * nor FastTree reports per-site steps.  Here the engine's own Fitch pass supplies them.
+ *   genes     as for pml_jackknife.  The concatenation is MSAConcatenator's: the sorted union of the genes' taxa, the genes in the
+ *             given order, a taxon a gene lacks is a row of '?'.  Nothing is concatenated as text.
+ *   newick    exactly the union's taxa; a rooted binary tree is unrooted first.  A polytomy other than a trifurcation at the top, a
+ *             missing or an extra taxon: PML_EPARSE.
+ *   steps[c]  the Fitch length of column c: tip sets are the state sets of the alignment codes, so '?', '-' and X are all 20
+ *             states, B = N|D, Z = Q|E, and an absent taxon is all states.
+ *   min_steps[c]  getMinimumStepsPerSite (SequenceAlignment.java:673-682 with getBipartitionsForAlignmentColumn :808-902): the
+ *             column's distinct Bipartitions less one.  Bytes are compared by identity over the n rows of the union.  With classes =
+ *             the distinct bytes other than '-' and '?' and shown = the rows showing neither: classes - 1 - [classes == 2 and
+ *             shown == n], the quirk PML_TRIM_UNIFORM documents (two classes that cover all rows are ONE bipartition); shown == n
+ *             needs the gene to hold every taxon of the union.  A column of nothing but '-' and '?' makes the Java dereference
+ *             null: PML_EPARSE naming gene and column.
+ *   totals    (:65-103) gene_steps and gene_beyond are the Java's int sums kept in 64 bits; gene_ratio is the Java's sequential
+ *             float sum of (float)steps / (float)(min_steps + 1) in column order.
+ * The genes are worked through in sub-batches that fit the HBM budget (0.85 of free HBM, or PML_HBM_BUDGET_MB); a single gene that
+ * does not fit is PML_ENOMEM with the size. */
+typedef struct {
+    int ngenes, ntax;
+    char **names;                     /* [ntax] the sorted union */
+    long long ncols;                  /* sum of the genes' columns */
+    long long *col_start;             /* [ngenes + 1] the Java's startStops */
+    int *steps, *min_steps;           /* [ncols] */
+    long long *gene_steps, *gene_beyond;   /* [ngenes] */
+    float *gene_ratio;                /* [ngenes] */
+} pml_gene_steps_result;
+int  pml_gene_steps(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const char *newick, pml_gene_steps_result *out);
+void pml_gene_steps_result_free(pml_gene_steps_result *result);
+/* The randomisation thresholds (:141-425).  Gene g's replicate is a sample of as many columns as g has, drawn from its domain: the
+ * columns of every gene h != g with !mask[h], in column order, U of them.  threshold[g] = the ascending-sorted replicate sums at
+ * index reps - k, k = (int)ceil(reps * alpha); n_ge[g] = the replicates whose sum is >= the gene's observed total.
+ *   statistic  the per-column table: steps, steps - min_steps, or the float ratio above
+ *   replace    1 = with replacement, 0 = without
+ *   multiple   > 0 and U < len_g * multiple: threshold[g] = -1 and n_ge[g] = -1, no error (the Java's "enough columns" rule)
+ * The Java's five methods: :141-176 = {RAW, 0, 0, no mask}; :178-213 = {BEYOND_MIN, 0, 0, no mask}; :240-307 (the current one) =
+ * {BEYOND_MIN, 1, 3, mask}; :309-365 (...OLD) = {BEYOND_MIN, 0, 2, mask}; :367-425 = {MIN_RATIO, 0, 2, mask}.
+ * PML_EINVAL: k outside [1, reps] (the Java indexes out of bounds); replace == 0, multiple == 0 and U < len_g (the Java loops for
+ * ever), naming the gene; ncols >= 2^31 or ngenes * reps >= 2^31.
+ * The draws are the library's own: the Java's generator is an unseeded java.util.Random, so its definitions are matched, not its
+ * stream.  base = (seed + 1) * 0x9E3779B97F4A7C15, key = base + ((g * reps + b) << 32) for replicate b.  With replacement draw j is
+ * the domain index ((mix64(key + j) >> 32) * U) >> 32.  Without replacement draw j is perm(mix64(key), U, j), a keyed bijection of
+ * [0, U): h = max(1, (bitlength(U - 1) + 1) / 2), x = L << h | R, four rounds (L, R) = (R, L ^ (mix64(K + (r << 40) + R) & (2^h - 1))),
+ * repeated while x >= U.  It yields a uniformly random len_g-subset of the domain, as the Java's rejection loop does; only the
+ * subset enters the sum.  int sums are exact, float sums are the Java's sequential chain in draw order. */
+enum { PML_STEPS_RAW = 0, PML_STEPS_BEYOND_MIN = 1, PML_STEPS_MIN_RATIO = 2 };
+typedef struct {
+    int statistic, replace, multiple, reps;
+    double alpha;
+    unsigned long long seed;
+    const unsigned char *mask;        /* [ngenes] or NULL */
+} pml_step_threshold_opts;
+int  pml_step_thresholds(pml_ctx *ctx, const pml_gene_steps_result *result, const pml_step_threshold_opts *opts, double *threshold /* [ngenes] */,
+                         long long *n_ge /* [ngenes], may be NULL */);
+/* host-only, needs no context: the concatenation columns that replicate `rep` of `gene` draws, in draw order, from the same draw
+ * functions (csrc/genesteps.hpp).  cols_out: the gene's number of columns.  A gene under the -1 rule: PML_EINVAL */
+int  pml_step_draws_host(const pml_step_threshold_opts *opts, int ngenes, const long long *col_start, int gene, int rep, long long *cols_out);
+/* test door of k_steps_resample: the kernel's sums of one gene, alone in its launch, unsorted.  sums: opts->reps values */
+int  pml_debug_step_replicates(pml_ctx *ctx, const pml_gene_steps_result *result, const pml_step_threshold_opts *opts, int gene, double *sums);
+/* launches on this context so far and, with cfg.profile = 1, summed HIP-event times in ms: [0] = k_fitch_sitesteps, [1] =
+ * k_steps_expand, [2] = k_colminsteps (each one per sub-batch of pml_gene_steps), [3] = k_steps_resample, [4] = k_steps_table (each
+ * one per pml_step_thresholds / pml_debug_step_replicates).  Never reset. */
+int  pml_gene_steps_stats(pml_ctx *ctx, long long *launches /* [5] */, double *total_ms /* [5] */);
+
 /* TreeComparison's `-rf` and `-tree_dist` legs (TreeComparison.java:48-50, compareAllvsAll :267-288) for a whole set of trees:
  * every pair (i, j), i < j, tree 1 = i, on the device (treecmp.hip).  The trees are given as Newick text and must all have the
  * same leaf labels (PML_EINVAL otherwise; at most 512 leaves, at least 3).

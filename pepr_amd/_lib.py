@@ -33,6 +33,8 @@ SYMBOLS = [
     "pml_debug_tree_pair_sums",
     "pml_trim_columns", "pml_trim_result_free", "pml_trim_congruence_filter", "pml_debug_column_flags", "pml_trim_column_flags_host",
     "pml_trim_stats",
+    "pml_gene_steps", "pml_gene_steps_result_free", "pml_step_thresholds", "pml_step_draws_host", "pml_debug_step_replicates",
+    "pml_gene_steps_stats",
 ]
 
 
@@ -150,6 +152,17 @@ class TrimResult(C.Structure):
     _ip = C.POINTER(C.c_int)
     _fields_ = [("ngenes", C.c_int), ("ntax", _ip), ("ncols", _ip), ("nkept", _ip), ("kept_cols", C.POINTER(_ip)),
                 ("rows", C.POINTER(C.POINTER(C.c_void_p))), ("gap_or_missing", C.POINTER(C.c_longlong))]
+
+
+class GeneStepsResult(C.Structure):
+    _ip, _lp = C.POINTER(C.c_int), C.POINTER(C.c_longlong)
+    _fields_ = [("ngenes", C.c_int), ("ntax", C.c_int), ("names", C.POINTER(C.c_char_p)), ("ncols", C.c_longlong), ("col_start", _lp),
+                ("steps", _ip), ("min_steps", _ip), ("gene_steps", _lp), ("gene_beyond", _lp), ("gene_ratio", C.POINTER(C.c_float))]
+
+
+class StepThresholdOpts(C.Structure):
+    _fields_ = [("statistic", C.c_int), ("replace", C.c_int), ("multiple", C.c_int), ("reps", C.c_int), ("alpha", C.c_double),
+                ("seed", C.c_ulonglong), ("mask", C.POINTER(C.c_ubyte))]
 
 
 _lib = None
@@ -286,5 +299,13 @@ def load():
     L.pml_debug_column_flags.argtypes = [vp, ap, C.POINTER(C.c_ubyte)]
     L.pml_trim_column_flags_host.argtypes = [ap, C.POINTER(C.c_ubyte)]
     L.pml_trim_stats.argtypes = [vp, lp, lp, dp]
+    gsp, stp = C.POINTER(GeneStepsResult), C.POINTER(StepThresholdOpts)
+    L.pml_gene_steps.argtypes = [vp, C.c_int, ap, C.c_char_p, gsp]
+    L.pml_gene_steps_result_free.argtypes = [gsp]
+    L.pml_gene_steps_result_free.restype = None
+    L.pml_step_thresholds.argtypes = [vp, gsp, stp, dp, lp]
+    L.pml_step_draws_host.argtypes = [stp, C.c_int, lp, C.c_int, C.c_int, lp]
+    L.pml_debug_step_replicates.argtypes = [vp, gsp, stp, C.c_int, dp]
+    L.pml_gene_steps_stats.argtypes = [vp, lp, dp]
     _lib = L
     return L

@@ -47,6 +47,7 @@ struct Ctx {
     long long newton_giveups = 0, newton_reissued = 0, newton_seq_launches = 0;   // k_newton fallback statistics (pml_newton_fallbacks)
     long long fitch_tips_launches = 0, fitch_launches = 0;      // k_fitch_tips and k_fitch launches (pml_fitch_stats)
     long long colclass_launches = 0, colgather_launches = 0; double trim_ms[3] = {0, 0, 0};   // pml_trim_stats: k_colclass, k_colgather, the uploads
+    long long gs_launches[5] = {0, 0, 0, 0, 0}; double gs_ms[5] = {0, 0, 0, 0, 0};   // pml_gene_steps_stats: k_fitch_sitesteps, k_steps_expand, k_colminsteps, k_steps_resample, k_steps_table
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;
     std::vector<hipEvent_t> pool;

@@ -241,6 +241,28 @@ struct TgGene { const uint8_t *in; uint8_t *out; const int *src_col; int ntax, n
 struct TgTile { int gene, chunk0, row0, pad; };
 void launch_colgather(const TgGene *genes, const TgTile *tiles, int ntiles, hipStream_t s);
 
+// The gene homoplasy test (genesteps.hip; rules in include/peprml.h, draw functions in genesteps.hpp).  A sub-batch's genes: raw
+// bytes in the CgGene layout (rows ld bytes apart) for k_colminsteps, site2pat for k_steps_expand; pat_off = the gene's first
+// pattern in the replicate of all genes of the sub-batch, col_base = its first column in the sub-batch's steps / min_steps.
+constexpr int GS_COLS = 256;          // columns per k_steps_expand / k_colminsteps workgroup, one per thread
+enum { GS_RAW = 0, GS_BEYOND = 1, GS_RATIO = 2 };
+struct GsGene { const uint8_t *bytes; const int *site2pat; int ntax, ncols, ld, pat_off; long long col_base; };
+// one Fitch operation on vectors of the pool ([vector][mpad]): a union of l and r counts one step; out >= 0: out = F(l, r)
+struct GsOp { int out, l, r, pad; };
+// pat_steps[p] = the unions pattern p takes over the nops operations, p < npat <= mpad
+void launch_fitch_sitesteps(const GsOp *ops, int nops, unsigned *pool, int mpad, int npat, int *pat_steps, hipStream_t s);
+// one workgroup per entry of tile_gene (GS_COLS columns of that gene, tile_first[gene] = its first tile), as launch_colclass
+void launch_steps_expand(const GsGene *genes, const int *tile_gene, const int *tile_first, int ntiles, const int *pat_steps, int *steps, hipStream_t s);
+// min_steps[col_base + column] = classes - 1 - [classes == 2 and shown == n_union]; -1: the column holds only '-' and '?'
+void launch_colminsteps(const GsGene *genes, const int *tile_gene, const int *tile_first, int ntiles, int n_union, int *min_steps, hipStream_t s);
+// table[i] = steps[i] (GS_RAW), steps[i] - mins[i] (GS_BEYOND), both int, or (float)steps[i] / (float)(mins[i] + 1) (GS_RATIO, float)
+void launch_steps_table(const int *steps, const int *mins, long long n, int statistic, void *table, hipStream_t s);
+// one gene of a resampling launch: len draws per replicate from a domain of U table indices; a domain index u reads table[u]
+// below split and table[u + len] from it on (a masked gene: split = U).  sums[entry * reps + b], int or float as the table
+struct GsEntry { int gene; uint32_t len, U, split; };
+void launch_steps_resample(const GsEntry *entries, int nentries, const void *table, void *sums, int reps, unsigned long long base, bool as_float, bool replace,
+                           hipStream_t s);
+
 // Tree-set comparison (treecmp.hip): the split records of T trees, compact: tree t owns entries off[t] .. off[t] + cnt[t] - 1 of
 // every array, its first nreal[t] are TreeBranches in the Java's order (treecmp.hpp).  id = interned split id, ln / lr =
 // length over the tree's maximum / the length itself, flags = TC_*; sid / sidx = the tree's (id, record index) pairs sorted

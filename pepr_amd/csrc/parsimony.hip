@@ -24,6 +24,7 @@
 #include <functional>
 
 #include "engine.hpp"
+#include "fitch_dev.hpp"
 
 namespace pml {
 
@@ -38,22 +39,7 @@ struct FRed { const int *partial; int *out; int nscores, nwaves; };
 typedef const unsigned __attribute__((address_space(1))) *gcu32;
 typedef unsigned __attribute__((address_space(1))) *gu32;
 
-// state set of an alignment code (host.hpp aa_code): the one table of the text path and of k_fitch_tips
-__host__ __device__ __forceinline__ unsigned code_mask(int c) {
-    if (c < 20) return 1u << c;
-    if (c == 20) return (1u << 2) | (1u << 3);     // B = N | D
-    if (c == 21) return (1u << 5) | (1u << 6);     // Z = Q | E
-    return 0xFFFFFu;
-}
-// one (replicate, gene) segment of k_fitch_tips: patterns [0, npat) of the gene go to [dst_off, dst_off + npat) of the replicate's
-// tip rows and weights; rowmap[t] = the gene's row of replicate taxon t, -1 = the gene lacks it.  src == null: the padding
-// segment [dst_off, dst_off + npat) = [sum of npat, mpad) of the replicate, every set bit and weight 0
-struct FTipSeg {
-    const uint8_t *src; const double *w; const int *rowmap; unsigned *pool; int *dst_w;
-    int src_mpad, npat, mpad, dst_off, ntax_dst, pad;
-};
-
-__device__ __forceinline__ unsigned fitch(unsigned l, unsigned r) { const unsigned x = l & r; return x ? x : (l | r); }
+// code_mask, FTipSeg and fitch: fitch_dev.hpp (shared with genesteps.hip)
 
 // sum over the 64 lanes, result uniform
 __device__ __forceinline__ int wave_sum(int v) {
@@ -124,7 +110,12 @@ __global__ __launch_bounds__(256) void k_fitch_tips(const FTipSeg *__restrict__ 
     }
 }
 
-#define PCHK(expr)                                                                                 \
+void launch_fitch_tips(const FTipSeg *segs, int nsegs, int max_npat, hipStream_t s) {
+    if (nsegs <= 0 || max_npat <= 0) return;
+    hipLaunchKernelGGL(k_fitch_tips, dim3((unsigned)nsegs, (unsigned)((max_npat + 255) / 256)), dim3(256), 0, s, segs);
+}
+
+#define PCHK(expr)                                                                          \
     do { hipError_t e_ = (expr);                                                                   \
          if (e_ != hipSuccess) return ctx->fail(-4, std::string("parsimony: ") + hipGetErrorString(e_)); } while (0)
 

@@ -18,6 +18,7 @@ NJ_DISTANCE, NJ_SIMILARITY = 0, 1      # pml_nj_from_matrix matrix types (TreeBu
 NJ_TREE, NJ_TOPOLOGY = 0, 1            # getNJTreeString (lengths) / getNJTopology (the `-nj true` path)
 TREE_ML, TREE_PARSIMONY, TREE_PARSIMONY_BL = 0, 1, 2      # pml_jackknife3 tree-building methods (PML_TREE_*)
 TRIM_UNIFORM, TRIM_GAP_UNIFORM, TRIM_TOPOLOGICAL = 0, 1, 2     # pml_trim_columns modes (PML_TRIM_*): MSATrimmer's three filters
+STEPS_RAW, STEPS_BEYOND_MIN, STEPS_MIN_RATIO = 0, 1, 2     # pml_step_thresholds statistics (PML_STEPS_*)
 EINVAL = -1
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
 
@@ -644,6 +645,58 @@ class Context:
         self._check(self.L.pml_trim_stats(self.ptr, C.byref(a), C.byref(b), ms))
         return {"class_launches": a.value, "gather_launches": b.value, "class_ms": ms[0], "gather_ms": ms[1], "upload_ms": ms[2]}
 
+    # ---- the gene homoplasy test of ConcatenatedSequenceAlignment (include/peprml.h pml_gene_steps, pml_step_thresholds) ----
+    def gene_steps(self, genes, newick):
+        """Per-column Fitch steps of the concatenation of `genes` on `newick`, the least steps each column can take, and the
+        Java's per-gene totals -> {"names" (the sorted union), "ncols", "col_start" int64[G + 1], "steps", "min_steps" int32[ncols],
+        "gene_steps", "gene_beyond" int64[G], "gene_ratio" float32[G]}.  Bytes are compared by identity for min_steps; a str row
+        stands for its latin-1 bytes."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_raw_aln_struct(g[0], g[1], keep) for g in genes])
+        res = _lib.GeneStepsResult()
+        self._check(self.L.pml_gene_steps(self.ptr, n, alns, newick.encode() if isinstance(newick, str) else newick, C.byref(res)))
+        try:
+            nc, G = res.ncols, res.ngenes
+            return {"names": [res.names[i].decode() for i in range(res.ntax)], "ncols": nc,
+                    "col_start": np.ctypeslib.as_array(res.col_start, (G + 1,)).copy(),
+                    "steps": np.ctypeslib.as_array(res.steps, (max(nc, 1),))[:nc].copy(),
+                    "min_steps": np.ctypeslib.as_array(res.min_steps, (max(nc, 1),))[:nc].copy(),
+                    "gene_steps": np.ctypeslib.as_array(res.gene_steps, (G,)).copy(),
+                    "gene_beyond": np.ctypeslib.as_array(res.gene_beyond, (G,)).copy(),
+                    "gene_ratio": np.ctypeslib.as_array(res.gene_ratio, (G,)).copy()}
+        finally:
+            self.L.pml_gene_steps_result_free(C.byref(res))
+
+    def step_thresholds(self, result, statistic=STEPS_BEYOND_MIN, replace=True, multiple=3, reps=1000, alpha=0.05, seed=0, mask=None):
+        """The randomisation thresholds of every gene of a gene_steps result -> {"threshold" float64[G] (-1: too few columns to
+        draw from), "n_ge" int64[G]: the replicates whose sum is >= the gene's observed total}.  The defaults are the Java's
+        current rule (:240-307)."""
+        res, keep = _gene_steps_struct(result)
+        o = _step_opts(statistic, replace, multiple, reps, alpha, seed, mask, res.ngenes, keep)
+        thr, nge = np.zeros(res.ngenes, dtype=np.float64), np.zeros(res.ngenes, dtype=np.int64)
+        self._check(self.L.pml_step_thresholds(self.ptr, C.byref(res), C.byref(o), _dp(thr), nge.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return {"threshold": thr, "n_ge": nge}
+
+    def debug_step_replicates(self, result, gene, statistic=STEPS_BEYOND_MIN, replace=True, multiple=3, reps=1000, alpha=0.05, seed=0, mask=None):
+        """Test door of k_steps_resample: the kernel's replicate sums of one gene, alone in its launch, unsorted -> float64[reps]"""
+        res, keep = _gene_steps_struct(result)
+        o = _step_opts(statistic, replace, multiple, reps, alpha, seed, mask, res.ngenes, keep)
+        sums = np.zeros(max(int(reps), 1), dtype=np.float64)
+        self._check(self.L.pml_debug_step_replicates(self.ptr, C.byref(res), C.byref(o), int(gene), _dp(sums)))
+        return sums[:int(reps)]
+
+    GENE_STEPS_KERNELS = ("fitch_sitesteps", "steps_expand", "colminsteps", "steps_resample", "steps_table")
+
+    def gene_steps_stats(self):
+        """launches of the gene-steps kernels on this context so far and (profile mode) their summed HIP-event times in ms"""
+        n, ms = (C.c_longlong * 5)(), (C.c_double * 5)()
+        self._check(self.L.pml_gene_steps_stats(self.ptr, n, ms))
+        out = {}
+        for k, name in enumerate(self.GENE_STEPS_KERNELS):
+            out[name + "_launches"], out[name + "_ms"] = n[k], ms[k]
+        return out
+
     # ---- TreeComparison's -rf / -tree_dist legs for a set of trees (include/peprml.h pml_tree_compare) ----
     TREE_COMPARE_ARRAYS = (("rf_legacy", 1, np.int32), ("rf_bipartition", 2, np.int32), ("rf_splits", 4, np.int32),
                            ("branch_dist", 8, np.float64), ("discrepant_dist", 16, np.float64))
@@ -1234,6 +1287,48 @@ def trim_column_flags_host(gene):
     if rc:
         raise PmlError(rc)
     return out[:a.nsites]
+
+
+def _gene_steps_struct(result):
+    """a gene_steps dict as the C struct the threshold calls read (the arrays stay the dict's; names are not needed)"""
+    G = len(result["col_start"]) - 1
+    keep = [np.ascontiguousarray(result[k], dtype=t) for k, t in (("col_start", np.int64), ("steps", np.int32), ("min_steps", np.int32),
+                                                                   ("gene_steps", np.int64), ("gene_beyond", np.int64), ("gene_ratio", np.float32))]
+    for a in (1, 2):
+        if keep[a].size == 0:
+            keep[a] = np.zeros(1, dtype=np.int32)
+    ip, lp = C.POINTER(C.c_int), C.POINTER(C.c_longlong)
+    res = _lib.GeneStepsResult(G, len(result.get("names", ())), None, int(keep[0][-1]) if G >= 0 and keep[0].size else 0, keep[0].ctypes.data_as(lp),
+                               keep[1].ctypes.data_as(ip), keep[2].ctypes.data_as(ip), keep[3].ctypes.data_as(lp), keep[4].ctypes.data_as(lp),
+                               keep[5].ctypes.data_as(C.POINTER(C.c_float)))
+    return res, keep
+
+
+def _step_opts(statistic, replace, multiple, reps, alpha, seed, mask, ngenes, keep):
+    m = None
+    if mask is not None:
+        if len(mask) != ngenes:
+            raise ValueError("mask needs one entry per gene")
+        m = (C.c_ubyte * max(ngenes, 1))(*[1 if x else 0 for x in mask])
+        keep.append(m)
+    return _lib.StepThresholdOpts(int(statistic), int(bool(replace)), int(multiple), int(reps), float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  C.cast(m, C.POINTER(C.c_ubyte)) if m is not None else None)
+
+
+def step_draws_host(col_start, gene, rep, statistic=STEPS_BEYOND_MIN, replace=True, multiple=3, reps=1000, alpha=0.05, seed=0, mask=None):
+    """pml_step_draws_host: the concatenation columns replicate `rep` of `gene` draws, in draw order, from the draw functions the
+    kernel runs (no device) -> int64 array of the gene's length"""
+    cs = np.ascontiguousarray(col_start, dtype=np.int64)
+    G = len(cs) - 1
+    keep = []
+    o = _step_opts(statistic, replace, multiple, reps, alpha, seed, mask, G, keep)
+    lp = C.POINTER(C.c_longlong)
+    n = int(cs[gene + 1] - cs[gene]) if 0 <= gene < G else 0
+    out = np.zeros(max(n, 1), dtype=np.int64)
+    rc = _lib.load().pml_step_draws_host(C.byref(o), G, cs.ctypes.data_as(lp), int(gene), int(rep), out.ctypes.data_as(lp))
+    if rc:
+        raise PmlError(rc)
+    return out[:n]
 
 
 def congruence_ktile():

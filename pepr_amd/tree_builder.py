@@ -377,6 +377,62 @@ class MSATrimmer:
         return self._trim(alignment, engine.TRIM_TOPOLOGICAL, None)
 
 
+class ConcatenatedSequenceAlignment:
+    """.../pepr/alignment/ConcatenatedSequenceAlignment.java's gene homoplasy test (:65-425) on the device (Context.gene_steps,
+    Context.step_thresholds; the rules are in include/peprml.h).  In the reference nothing ever calls setStepsPerSite
+    (SequenceAlignment.java:1033), so these methods have no input there; here `tree`, the tree of the concatenation, supplies
+    the per-site steps through the engine's Fitch pass.  Every method answers for one alignmentIndex as the Java does, but all
+    genes are computed in one call and cached per option set.  The Java draws from an unseeded java.util.Random; here the
+    draws are the library's own, a function of `seed`.  alignmentMask: one boolean per gene."""
+
+    def __init__(self, genes, tree, ctx=None, seed=0):
+        self.genes = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
+        self.tree, self.ctx, self.seed = tree, ctx, seed
+        self._steps, self._thresholds = None, {}
+
+    def _result(self):
+        if self._steps is None:
+            self._steps = (self.ctx or default_context()).gene_steps(self.genes, self.tree)
+        return self._steps
+
+    def getStepsPerSite(self):
+        return self._result()["steps"]
+
+    def getMinimumStepsPerSite(self):
+        return self._result()["min_steps"]
+
+    def getStepsForAlignment(self, alignmentIndex):
+        return int(self._result()["gene_steps"][alignmentIndex])
+
+    def getTotalStepsBeyondMinimumForAlignment(self, alignmentIndex):
+        return int(self._result()["gene_beyond"][alignmentIndex])
+
+    def getTotalStepsToMinimumRatioForAlignment(self, alignmentIndex):
+        return float(self._result()["gene_ratio"][alignmentIndex])
+
+    def _threshold(self, alignmentIndex, statistic, replace, multiple, reps, alpha, mask):
+        key = (statistic, replace, multiple, int(reps), float(alpha), None if mask is None else tuple(bool(m) for m in mask))
+        if key not in self._thresholds:
+            ctx = self.ctx or default_context()
+            self._thresholds[key] = ctx.step_thresholds(self._result(), statistic, replace, multiple, reps, alpha, self.seed, mask)
+        return self._thresholds[key]["threshold"][alignmentIndex]
+
+    def getThresholdStepsForAlignment(self, alignmentIndex, reps, alpha):
+        return int(self._threshold(alignmentIndex, engine.STEPS_RAW, False, 0, reps, alpha, None))
+
+    def getThresholdStepsBeyondMinimumForAlignment(self, alignmentIndex, reps, alpha, alignmentMask=None):
+        """without a mask :178-213 (no replacement); with one :240-307, the current rule (replacement, multiple 3)"""
+        if alignmentMask is None:
+            return int(self._threshold(alignmentIndex, engine.STEPS_BEYOND_MIN, False, 0, reps, alpha, None))
+        return int(self._threshold(alignmentIndex, engine.STEPS_BEYOND_MIN, True, 3, reps, alpha, alignmentMask))
+
+    def getThresholdStepsBeyondMinimumForAlignmentOLD(self, alignmentIndex, reps, alpha, alignmentMask):
+        return int(self._threshold(alignmentIndex, engine.STEPS_BEYOND_MIN, False, 2, reps, alpha, alignmentMask))
+
+    def getThresholdStepsToMinimumRatioForAlignment(self, alignmentIndex, reps, alpha, alignmentMask):
+        return float(self._threshold(alignmentIndex, engine.STEPS_MIN_RATIO, False, 2, reps, alpha, alignmentMask))
+
+
 class TreeComparison:
     """.../pepr/tree/TreeComparison.java:812-885 runConsel: `raxmlHPC -f g` on the trees, then `makermt -b 10 --puzzle`, `consel`
     and `catpv -v` on its per-site lnL -- here one engine call (pml_tree_tests, or pml_tree_tests_weighted).  weighted=True returns

@@ -9,7 +9,7 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
                          [--full-tree-method ml|parsimony|parsimony_bl|nj] [--support-tree-method ml|FastTree|parsimony|nj]
-                         [-uniform_trim] [-congruence_filter] [-trim_percent 0.1]
+                         [-uniform_trim] [-congruence_filter] [-trim_percent 0.1] [-gene_steps [REPS ALPHA]]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
                   PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
@@ -33,6 +33,12 @@ usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-se
                   include/peprml.h (PML_TRIM_UNIFORM).  Writes <run>.trim.tsv: file, columns, kept -- one row per gene; a gene trimmed
                   to 0 columns is dropped with a message.  With -congruence_filter the genes are uploaded once and trimmed and
                   filtered in one call (pml_trim_congruence_filter)
+-gene_steps [REPS ALPHA]   the gene homoplasy test of ConcatenatedSequenceAlignment.java (include/peprml.h pml_gene_steps) on the full
+                  tree just built: per gene the Fitch steps of its columns, the steps beyond the minimum, the steps-to-minimum
+                  ratio, and the threshold of the Java's current rule (steps beyond the minimum, REPS samples with replacement from
+                  the other genes' columns, the ceil(REPS * ALPHA)-th largest; -1 when the others hold fewer than three times the
+                  gene's columns) with n_ge, the samples at or above the gene's own total.  Defaults 1000 and 0.05; the draws take
+                  -seed.  Writes <run>.steps.tsv: gene, columns, steps, beyond, ratio, threshold, n_ge -- one row per gene
 Without these flags the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
 """
 import glob
@@ -59,6 +65,7 @@ def read_fasta(path):
 
 def main(argv):
     args = {}
+    gene_steps_vals = None
     i = 0
     while i < len(argv):                       # CommandLineProperties style: -flag value
         if argv[i].startswith("-"):
@@ -67,6 +74,8 @@ def main(argv):
             while i < len(argv) and not argv[i].startswith("-"):
                 vals.append(argv[i]); i += 1
             args[key] = vals[0] if vals else "true"
+            if key == "gene_steps":
+                gene_steps_vals = vals
         else:
             i += 1
     if "run_name" not in args or "alignment_dir" not in args:
@@ -110,6 +119,7 @@ def main(argv):
                     print("discarding set %s cost: %d" % (os.path.basename(name), mc))
         genes = [g for g, k in zip(genes, r["keep"]) if k]
         print("Discarded: %d\tKept: %d" % (len(files) - len(genes), len(genes)))
+        files = [f for f, k in zip(files, r["keep"]) if k]
     t0 = time.time()
     if {"full_tree_method", "support_tree_method"} & set(args):
         from pepr_amd import tree_builder
@@ -133,6 +143,16 @@ def main(argv):
     run = args["run_name"]
     open(run + ".nwk", "w").write(r["newick"] + "\n")
     open(run + ".sup", "w").write("\n".join(r["support_trees"]) + "\n")
+    if gene_steps_vals is not None:             # the gene homoplasy test on the tree just built
+        g_reps = int(gene_steps_vals[0]) if len(gene_steps_vals) > 0 else 1000
+        g_alpha = float(gene_steps_vals[1]) if len(gene_steps_vals) > 1 else 0.05
+        gs = ctx.gene_steps(genes, r["newick"])
+        th = ctx.step_thresholds(gs, engine.STEPS_BEYOND_MIN, True, 3, g_reps, g_alpha, int(args.get("seed", 1)))
+        with open(run + ".steps.tsv", "w") as f:
+            f.write("gene\tcolumns\tsteps\tbeyond\tratio\tthreshold\tn_ge\n")
+            for k, name in enumerate(files):
+                f.write("%s\t%d\t%d\t%d\t%s\t%d\t%d\n" % (os.path.basename(name), gs["col_start"][k + 1] - gs["col_start"][k], gs["gene_steps"][k],
+                                                         gs["gene_beyond"][k], repr(float(gs["gene_ratio"][k])), int(th["threshold"][k]), th["n_ge"][k]))
     if "lnl" not in r:                          # the NJ loop: no likelihood
         print("%s: %d genes, neighbor joining, %d support trees, %.2f s -> %s.nwk %s.sup" % (run, len(genes), reps, dt, run, run))
         return
