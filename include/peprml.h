@@ -444,6 +444,64 @@ int pml_parsimony_batch(pml_ctx *ctx, int n, const pml_alignment *alns, const pm
 int pml_bootstrap(pml_ctx *ctx, const pml_alignment *aln, const pml_model *model, int reps, unsigned long long seed,
                   int spr_radius_best, double epsilon, pml_result *best_out,
                   char **replicate_newicks_out /* optional: reps lines; pml_free */);
+/* The column bootstrap of a gene set as a resident call: `raxmlHPC -f a -x seed -N reps` (PML_TREE_ML) and `-Y -N reps`
+ * (PML_TREE_PARSIMONY, PML_TREE_PARSIMONY_BL) on the concatenation of `genes` (taxa = sorted union, a gene that lacks a taxon
+ * contributes gaps), the path PhylogenomicPipeline2.buildConcatenatedTree (:836-890) takes with bootstrapReps through
+ * PhylogeneticTreeBuilder.java:136-181.  The genes are encoded once into HBM; no resampled text is built.
+ *   column space   the genes in the order given: L = sum of nsites columns, P = sum of npat patterns (compressed per gene, never
+ *             across genes); column c of gene g with local site s has pattern id off_g + site2pat_g[s].
+ *   draws     replicate r has the key K_r = mix64((seed + 1) * 0x9E3779B97F4A7C15 + r), mix64 = splitmix64's finaliser; draw j
+ *             (0 <= j < L) is column c_j = ((mix64(K_r + j) >> 32) * L) >> 32, the multiply-shift rule of pml_step_thresholds.
+ *             count[r][p] = the draws that land on pattern p (sum = L); replicate r is the patterns with count > 0 in ascending
+ *             p, each with weight count[r][p], padded to a multiple of 32 patterns with weightless gaps.  The draws are the
+ *             project's own (RAxML's -x stream lives inside its binary): parity unpinned, as for pml_step_thresholds.
+ *   best tree      PML_TREE_ML: NNI + SPR within spr_radius_best on the replicate of all genes, as pml_jackknife* builds its full
+ *             tree.  PML_TREE_PARSIMONY: the parsimony tree of all genes, topology only; lnl, alpha, tree_length 0.
+ *             PML_TREE_PARSIMONY_BL: that topology, then lengths and alpha optimised under `model` (`-f e`).
+ *   replicates     PML_TREE_ML: the NNI search from the neighbour-joining tree of the replicate's weighted pair counts, under
+ *             replicate_model.  Parsimony (both methods): parsimony trees within parsimony_radius, returned topology only --
+ *             nothing reads their lengths.  Stepwise-addition seeds: the best tree (unsigned)seed, replicate r (unsigned)(seed +
+ *             1 + r), 0 replaced by 0x9E3779B9, as pml_jackknife3.  The replicates go through in sub-batches sized against free
+ *             HBM; the result does not depend on the split.
+ *   labels    best_out->newick carries (int)(0.5 + 100 c / reps) per bipartition, c = the replicate trees that contain it, as
+ *             pml_bootstrap; with reps == 0 it carries no labels.  npatterns = P, nsites = L.
+ * RAxML's rapid-bootstrap shortcuts (CAT approximation, tree reuse between replicates) and whatever files `-Y -N` writes are not
+ * restated: every replicate gets a search of its own.  PML_EINVAL with a message: reps < 0, an unknown method, fewer than 3 taxa
+ * in the union, L < 1 or L >= 2^31.  opts NULL = 100 ML replicates, seed 0, radius 5 / 20. */
+typedef struct {
+    int reps; int method;              /* PML_TREE_ML | PML_TREE_PARSIMONY | PML_TREE_PARSIMONY_BL */
+    unsigned long long seed;
+    int spr_radius_best;               /* ML best tree, as pml_bootstrap */
+    int parsimony_radius;              /* as pml_jackknife_opts3 */
+    double epsilon;                    /* 0 = 1e-3 */
+    const pml_model *replicate_model;  /* NULL = model; any code pml_jackknife2 accepts */
+} pml_bootstrap_opts2;
+int pml_bootstrap2(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_model *model, const pml_bootstrap_opts2 *opts,
+                   pml_result *best_out, char **replicate_newicks_out /* optional: reps lines; pml_free */,
+                   long long *mp_lengths_out /* optional, 1 + reps: [0] best tree, [1 + r] replicate r; -1 = not a parsimony tree */);
+/* the log likelihoods the ML replicates of the last pml_bootstrap2 call on this context ended their searches with, in replicate
+ * order (their Newick lines carry none): writes min(n, count) values, returns the count.  The values are state of the context:
+ * every pml_bootstrap2 call clears them on entry, so the count is 0 after a parsimony call, a refused call, or none; after a call
+ * that failed part-way it counts the sub-batches that finished */
+int pml_boot_replicate_lnls(pml_ctx *ctx, int n, double *lnl_out);
+/* host-only, no context: the ncols columns replicate `rep` of a call with `seed` draws, in draw order, from the functions the
+ * kernel runs (csrc/boot.hpp).  PML_EINVAL: rep < 0, ncols < 1 or ncols >= 2^31 */
+int pml_boot_draws_host(unsigned long long seed, int rep, long long ncols, unsigned *cols_out);
+/* the patterns k_boot_index compacts per step of its scan */
+int pml_boot_tile(void);
+/* test door: what the device builds for replicate `rep` of the selection `sel` (NULL = all genes), read back.  idx_out[npat] = the
+ * replicate's pattern ids, ascending; form 0: cells_out = the code matrix uint8 [ntax x mpad] (padding = the gap code 22),
+ * weights_out = f64 [mpad] (padding 0), as an ML batch holds them; form 1: cells_out = the Fitch state sets uint32 [ntax x mpad]
+ * (padding 0xFFFFF), weights_out = int [mpad], as a parsimony pool holds them (mpad >= 32); cmp_out / diff_out [ntax x ntax] = the
+ * weighted comparable / differing column counts of every taxon pair (k_boot_pairs; from the form 0 build in both forms, so form 1
+ * runs count, index and gather twice).  names_out: one taxon per line.  Everything returned is freed with pml_free. */
+int pml_debug_boot_replicate(pml_ctx *ctx, int ngenes, const pml_alignment *genes, int nsel, const int *sel, unsigned long long seed,
+                             int rep, int form, int *ntax_out, int *npat_out, int *mpad_out, int **idx_out, void **cells_out,
+                             void **weights_out, long long **cmp_out, long long **diff_out, char **names_out);
+/* launches on this context so far: [0] k_boot_count, [1] k_boot_index, [2] k_boot_gather, [3] k_boot_pairs; with cfg.profile = 1
+ * kernel_ms holds their summed HIP-event times; build_ms = the host wall time of the replicate builds (count, index, layout,
+ * gather, pair counts and NJ starts, or the tip rows of a pool).  Any pointer may be NULL.  Never reset. */
+int pml_boot_stats(pml_ctx *ctx, long long *launches /* [4] */, double *kernel_ms /* [4] */, double *build_ms);
 /* host-only: FASTA text (">taxon\nSEQ\n" per taxon, SequenceAlignment.java:405-416) of the
  * concatenation of the selected genes (sel == NULL: all), taxa = sorted union, '?' padding */
 int pml_concatenate(int ngenes, const pml_alignment *genes, int nsel, const int *sel, char **fasta_out);

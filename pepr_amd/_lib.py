@@ -35,6 +35,8 @@ SYMBOLS = [
     "pml_trim_stats",
     "pml_gene_steps", "pml_gene_steps_result_free", "pml_step_thresholds", "pml_step_draws_host", "pml_debug_step_replicates",
     "pml_gene_steps_stats",
+    "pml_bootstrap2", "pml_boot_draws_host", "pml_boot_tile", "pml_debug_boot_replicate", "pml_boot_stats",
+    "pml_boot_replicate_lnls",
 ]
 
 
@@ -105,6 +107,11 @@ class JackknifeOpts2(C.Structure):
 class JackknifeOpts3(C.Structure):
     _fields_ = [("base2", JackknifeOpts2), ("full_method", C.c_int), ("support_method", C.c_int), ("parsimony_radius", C.c_int),
                 ("pad", C.c_int)]
+
+
+class BootstrapOpts2(C.Structure):
+    _fields_ = [("reps", C.c_int), ("method", C.c_int), ("seed", C.c_ulonglong), ("spr_radius_best", C.c_int),
+                ("parsimony_radius", C.c_int), ("epsilon", C.c_double), ("replicate_model", C.POINTER(Model))]
 
 
 class ParsimonyOpts(C.Structure):
@@ -307,5 +314,11 @@ def load():
     L.pml_step_draws_host.argtypes = [stp, C.c_int, lp, C.c_int, C.c_int, lp]
     L.pml_debug_step_replicates.argtypes = [vp, gsp, stp, C.c_int, dp]
     L.pml_gene_steps_stats.argtypes = [vp, lp, dp]
+    L.pml_bootstrap2.argtypes = [vp, C.c_int, ap, mp, C.POINTER(BootstrapOpts2), rp, C.POINTER(vp), lp]
+    L.pml_boot_draws_host.argtypes = [C.c_ulonglong, C.c_int, C.c_longlong, C.POINTER(C.c_uint)]
+    L.pml_boot_tile.argtypes = []
+    L.pml_debug_boot_replicate.argtypes = [vp, C.c_int, ap, C.c_int, ip, C.c_ulonglong, C.c_int, C.c_int, ip, ip, ip] + [C.POINTER(vp)] * 6
+    L.pml_boot_stats.argtypes = [vp, lp, dp, dp]
+    L.pml_boot_replicate_lnls.argtypes = [vp, C.c_int, dp]
     _lib = L
     return L

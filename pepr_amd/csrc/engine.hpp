@@ -48,6 +48,10 @@ struct Ctx {
     long long fitch_tips_launches = 0, fitch_launches = 0;      // k_fitch_tips and k_fitch launches (pml_fitch_stats)
     long long colclass_launches = 0, colgather_launches = 0; double trim_ms[3] = {0, 0, 0};   // pml_trim_stats: k_colclass, k_colgather, the uploads
     long long gs_launches[5] = {0, 0, 0, 0, 0}; double gs_ms[5] = {0, 0, 0, 0, 0};   // pml_gene_steps_stats: k_fitch_sitesteps, k_steps_expand, k_colminsteps, k_steps_resample, k_steps_table
+    // pml_boot_stats: k_boot_count, k_boot_index, k_boot_gather, k_boot_pairs launches, (profile mode) their HIP-event times, and the
+    // host wall time of the replicate builds (count .. NJ starts / tip rows)
+    long long boot_launches[4] = {0, 0, 0, 0}; double boot_ms[4] = {0, 0, 0, 0}, boot_build_ms = 0;
+    std::vector<double> boot_last_lnl;                           // the ML replicates' lnL of the last pml_bootstrap2 call (pml_boot_replicate_lnls)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;
     std::vector<hipEvent_t> pool;
@@ -152,6 +156,7 @@ struct Search2Opts { bool nni = true, opt_alpha = true; double eps = 1e-3; bool 
 // branch ts and the two halves tg, th of the split edge optimised (in: start values; out: what the sweeps settled on), score =
 // the lnL of that tree with nothing else touched
 struct ThoroughJob { int g, p, ks; SprCandidate cand; double ts, tg, th, score; int sweeps; };
+struct BootSet; struct BootDebug;    // boot_dev.hpp / below: the column bootstrap
 struct Batch {
     Ctx *ctx = nullptr;
     int pi_mode = 0, ncat = 4, det_id = 0;
@@ -256,6 +261,13 @@ struct Batch {
     // the summed pair counts: no column text is touched again.  A per-gene code (empirical frequencies, GTR) gives every
     // replicate its own model, its frequencies counted on the device (k_codehist)
     int create_replicates(Ctx *c, const GeneStore &store, const std::vector<std::vector<int>> &sel, int pi_mode, int ncat, double alpha);
+    // the counterpart for the column bootstrap (boot.cpp): one batch gene per replicate [reps_begin, reps_end) of the call with
+    // `seed` over the concatenation of the selected store genes.  A replicate is the patterns its draws hit, compacted in
+    // ascending order, each weighted by its number of draws (boot.hpp); count, index, read-back of the pattern counts, layout,
+    // gather, pair counts and NJ starts, all from the resident genes.  set: the selection's column space when the caller keeps
+    // one for several sub-batches (null = built here); dbg: replicate reps_begin's idx and pair counts for the test door
+    int create_bootstrap(Ctx *c, const GeneStore &store, const std::vector<int> &sel, int reps_begin, int reps_end, unsigned long long seed,
+                         int pi_mode, int ncat, double alpha, const struct BootSet *set = nullptr, struct BootDebug *dbg = nullptr);
     int layout(double alpha, bool score_only);
     void destroy();
 
@@ -341,5 +353,15 @@ int parsimony_replicates(Ctx *ctx, const GeneStore &store, const std::vector<std
 // test door: the tip rows [ntax x mpad] and weights [mpad] k_fitch_tips writes for one selection
 int fitch_tips_readback(Ctx *ctx, const GeneStore &store, const std::vector<int> &sel, int *npat_out, int *mpad_out, std::vector<unsigned> &masks_out,
                         std::vector<int> &weights_out, std::vector<std::string> &names_out);
+
+// the column bootstrap's parsimony trees (parsimony.hip): replicates [reps_begin, reps_end) of the call with `seed` over the
+// selection's column space, their tip rows and weights written by k_boot_gather; replicate r gets the stepwise-addition seed
+// boot_parsimony_seed(seed, 1 + r).  All replicates cover set.names
+int parsimony_bootstrap(Ctx *ctx, const struct BootSet &set, int reps_begin, int reps_end, unsigned long long seed, int radius,
+                        std::vector<Tree> &trees_out, std::vector<long long> &lengths_out);
+// test door: the tip rows [ntax x mpad] and weights [mpad] of one bootstrap replicate
+int boot_tips_readback(Ctx *ctx, const struct BootSet &set, int rep, unsigned long long seed, int *npat_out, int *mpad_out,
+                       std::vector<unsigned> &masks_out, std::vector<int> &weights_out);
+struct BootDebug { std::vector<int> idx; std::vector<int64_t> cmp, diff; };
 
 }  // namespace pml

@@ -16,13 +16,16 @@
 // the waves.  The algorithm (addition order, enumeration orders, tie breaks) is the one spelled out in
 // oracle/pml_oracle.c so results are bit-identical to the oracle.
 //
-// The tip vectors come from one of two sources: alignment text encoded on the host (pml_parsimony*), or the genes that a
+// The tip vectors come from one of three sources: alignment text encoded on the host (pml_parsimony*), or the genes that a
 // jackknife keeps resident in HBM (GeneStore): k_fitch_tips writes the tip rows and weights of every replicate of a
-// sub-batch straight from the genes' code matrices, one launch, no concatenated text and no replicate code matrix.
+// sub-batch straight from the genes' code matrices, one launch, no concatenated text and no replicate code matrix; or the
+// column bootstrap's replicates of such genes (pml_bootstrap2): k_boot_gather (boot.hip) writes the patterns a replicate's draws
+// hit, weighted by their number of draws.
 #include <algorithm>
 #include <cstring>
 #include <functional>
 
+#include "boot_dev.hpp"
 #include "engine.hpp"
 #include "fitch_dev.hpp"
 
@@ -451,6 +454,58 @@ int parsimony_replicates(Ctx *ctx, const GeneStore &store, const std::vector<std
     if (int rc = parsimony_core(ctx, G, seeds, radius, lengths_out, moves)) return rc;
     trees_out.resize(n); names_out.resize(n);
     for (int g = 0; g < n; ++g) { trees_out[g] = G[g].tree; names_out[g] = std::move(G[g].aln.names); }
+    return 0;
+}
+
+// Tip source of the column bootstrap: G[i] = replicate begin + i of the call with `seed` over the column space `set` -- the
+// patterns its draws hit, in ascending order, each weighted by its number of draws (boot.hpp).  Count and index first (the pools
+// are sized by the pattern counts read back), then ONE k_boot_gather launch writes the tip rows and weights of all of G, padding
+// included.  Every replicate covers set.names.
+static int bootstrap_tips(Ctx *ctx, const BootSet &set, BootReps &br, int begin, int end, unsigned long long seed, int radius, std::vector<PGene> &G) {
+    const double t0 = now_ms();
+    if (int rc = br.count_and_index(ctx, set, begin, end, seed)) return rc;
+    G.resize((size_t)br.n);
+    for (int r = 0; r < br.n; ++r) {
+        EncodedAlignment &A = G[r].aln;
+        A.names = set.names; A.ntax = (int)set.names.size(); A.nsites = (int)set.L; A.npat = br.npat[r];
+        A.mpad = std::max(32, (A.npat + 31) / 32 * 32);
+    }
+    if (int rc = alloc_pools(ctx, G, radius)) return rc;
+    for (int r = 0; r < br.n; ++r) { br.h[r].dst = G[r].d_pool; br.h[r].dst_w = G[r].d_w; br.h[r].mpad = G[r].aln.mpad; }   // the pool's first ntax vectors are the tips
+    if (int rc = br.gather(BOOT_FORM_MASKS)) return rc;
+    ctx->boot_build_ms += now_ms() - t0;
+    return 0;
+}
+
+int parsimony_bootstrap(Ctx *ctx, const BootSet &set, int reps_begin, int reps_end, unsigned long long seed, int radius,
+                        std::vector<Tree> &trees_out, std::vector<long long> &lengths_out) {
+    PCHK(hipSetDevice(ctx->device));
+    std::vector<PGene> G;
+    FreePools freer{G};
+    BootReps br;
+    if (int rc = bootstrap_tips(ctx, set, br, reps_begin, reps_end, seed, radius, G)) return rc;
+    br.destroy();                                                 // counts and indices are not read again
+    std::vector<unsigned> seeds;
+    for (int r = reps_begin; r < reps_end; ++r) seeds.push_back(boot_parsimony_seed(seed, 1 + r));
+    std::vector<int> moves;
+    if (int rc = parsimony_core(ctx, G, seeds, radius, lengths_out, moves)) return rc;
+    trees_out.resize(G.size());
+    for (size_t g = 0; g < G.size(); ++g) trees_out[g] = G[g].tree;
+    return 0;
+}
+
+int boot_tips_readback(Ctx *ctx, const BootSet &set, int rep, unsigned long long seed, int *npat_out, int *mpad_out,
+                       std::vector<unsigned> &masks_out, std::vector<int> &weights_out) {
+    PCHK(hipSetDevice(ctx->device));
+    std::vector<PGene> G;
+    FreePools freer{G};
+    BootReps br;
+    if (int rc = bootstrap_tips(ctx, set, br, rep, rep + 1, seed, 0, G)) return rc;
+    const PGene &pg = G[0];
+    masks_out.resize((size_t)pg.aln.ntax * pg.aln.mpad); weights_out.resize((size_t)pg.aln.mpad);
+    PCHK(hipMemcpy(masks_out.data(), pg.d_pool, masks_out.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    PCHK(hipMemcpy(weights_out.data(), pg.d_w, weights_out.size() * sizeof(int), hipMemcpyDeviceToHost));
+    *npat_out = pg.aln.npat; *mpad_out = pg.aln.mpad;
     return 0;
 }
 

@@ -338,6 +338,68 @@ class Context:
             self.L.pml_free(rep)
         return out
 
+    def bootstrap2(self, genes, reps=100, seed=1, method=TREE_ML, spr_radius=5, parsimony_radius=20, epsilon=1e-3, alpha=1.0, ncat=4,
+                   pi_mode=PI_RAXML_3DP, replicate_pi_mode=None, replicate_alpha=None):
+        """pml_bootstrap2: the column bootstrap of a gene set (`-f a -x seed -N reps`, `-Y -N reps`) with every replicate built on
+        the device from the genes resident in HBM.  genes: list of (names, rows), possibly over different taxon subsets.
+        -> bootstrap()'s dict plus "npatterns", "nsites" and "mp_lengths" (1 + reps: [0] the best tree, -1 = not a parsimony tree)."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        m = _model(ncat, alpha, pi_mode)
+        rm = None
+        if replicate_pi_mode is not None or replicate_alpha is not None:
+            rm = _model(ncat, alpha if replicate_alpha is None else replicate_alpha, pi_mode if replicate_pi_mode is None else replicate_pi_mode)
+        o = _lib.BootstrapOpts2(int(reps), int(method), int(seed) & 0xFFFFFFFFFFFFFFFF, int(spr_radius), int(parsimony_radius), float(epsilon),
+                                C.pointer(rm) if rm is not None else None)
+        res, rep = _lib.Result(), C.c_void_p()
+        mp = (C.c_longlong * (1 + max(int(reps), 0)))()
+        rc = self.L.pml_bootstrap2(self.ptr, n, alns, C.byref(m), C.byref(o), C.byref(res), C.byref(rep), mp)
+        self._check(rc)
+        out = {"lnl": res.lnl, "alpha": res.alpha, "tree_length": res.tree_length, "npatterns": res.npatterns, "nsites": res.nsites,
+               "newick": C.string_at(res.newick).decode(), "replicates": C.string_at(rep).decode().splitlines() if rep else [],
+               "mp_lengths": [int(v) for v in mp]}
+        self.L.pml_result_free(C.byref(res))
+        if rep:
+            self.L.pml_free(rep)
+        lnls = (C.c_double * max(int(reps), 1))()
+        have = self.L.pml_boot_replicate_lnls(self.ptr, max(int(reps), 0), lnls)
+        out["replicate_lnl"] = [float(lnls[i]) for i in range(max(have, 0))]       # ML replicates only: a parsimony tree has none
+        return out
+
+    def debug_boot_replicate(self, genes, sel=None, seed=1, rep=0, form=0):
+        """Test door of the bootstrap kernels: what the device builds for replicate `rep` of the selection (None = all genes)
+        -> {"names", "npat", "mpad", "idx" int32[npat], "cells" uint8 (form 0: codes) or uint32 (form 1: state sets) [ntax, mpad],
+        "weights" float64 (form 0) or int32 (form 1) [mpad], "cmp", "diff" int64[ntax, ntax]}; padding included."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_aln_struct(g[0], g[1], keep) for g in genes])
+        nt, npat, mpad = C.c_int(), C.c_int(), C.c_int()
+        ptrs = [C.c_void_p() for _ in range(6)]                     # idx, cells, weights, cmp, diff, names
+        arr = (C.c_int * len(sel))(*sel) if sel is not None else None
+        rc = self.L.pml_debug_boot_replicate(self.ptr, n, alns, len(sel) if sel is not None else 0, arr, int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep),
+                                             int(form), C.byref(nt), C.byref(npat), C.byref(mpad), *[C.byref(p) for p in ptrs])
+        self._check(rc)
+        t, m = nt.value, mpad.value
+        cdt, wdt = (np.uint8, np.float64) if form == 0 else (np.uint32, np.int32)
+        out = {"names": C.string_at(ptrs[5]).decode().splitlines(), "npat": npat.value, "mpad": m,
+               "idx": np.frombuffer(C.string_at(ptrs[0], 4 * npat.value), dtype=np.int32).copy(),
+               "cells": np.frombuffer(C.string_at(ptrs[1], np.dtype(cdt).itemsize * t * m), dtype=cdt).reshape(t, m).copy(),
+               "weights": np.frombuffer(C.string_at(ptrs[2], np.dtype(wdt).itemsize * m), dtype=wdt).copy(),
+               "cmp": np.frombuffer(C.string_at(ptrs[3], 8 * t * t), dtype=np.int64).reshape(t, t).copy(),
+               "diff": np.frombuffer(C.string_at(ptrs[4], 8 * t * t), dtype=np.int64).reshape(t, t).copy()}
+        for p in ptrs:
+            self.L.pml_free(p)
+        return out
+
+    def boot_stats(self):
+        """launches of k_boot_count, k_boot_index, k_boot_gather, k_boot_pairs on this context so far, their summed HIP-event
+        times in ms (profile mode) and the host wall time of the replicate builds"""
+        n, ms, wall = (C.c_longlong * 4)(), (C.c_double * 4)(), C.c_double()
+        self._check(self.L.pml_boot_stats(self.ptr, n, ms, C.byref(wall)))
+        keys = ("count", "index", "gather", "pairs")
+        return {"launches": dict(zip(keys, (int(v) for v in n))), "ms": dict(zip(keys, (float(v) for v in ms))), "build_ms": wall.value}
+
     def parsimony(self, genes, seed=0, spr_radius=20):
         """`raxmlHPC -y` start trees (RAxMLRunner.java:215-251): list of {"newick" (topology only), "length"}."""
         keep = []
@@ -1329,6 +1391,21 @@ def step_draws_host(col_start, gene, rep, statistic=STEPS_BEYOND_MIN, replace=Tr
     if rc:
         raise PmlError(rc)
     return out[:n]
+
+
+def boot_draws_host(seed, rep, ncols):
+    """pml_boot_draws_host: the ncols columns replicate `rep` of a bootstrap2 call with `seed` draws, in draw order, from the
+    functions the kernel runs (no device) -> uint32 array"""
+    out = np.zeros(max(int(ncols), 1) if int(ncols) < (1 << 31) else 1, dtype=np.uint32)
+    rc = _lib.load().pml_boot_draws_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep), int(ncols), out.ctypes.data_as(C.POINTER(C.c_uint)))
+    if rc:
+        raise PmlError(rc, "rep %r, ncols %r" % (rep, ncols))
+    return out[:ncols]
+
+
+def boot_tile():
+    """the patterns k_boot_index compacts per step of its scan"""
+    return _lib.load().pml_boot_tile()
 
 
 def congruence_ktile():

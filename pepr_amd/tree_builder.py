@@ -21,8 +21,9 @@ read like the reference's own call sites; every `run()` goes through the C ABI
 Behaviour kept from the reference: a failed build leaves the result `None` (FastTreeRunner.java:
 125-131 logs and continues; callers see a null tree string); the ML matrix is a RAxML model
 string (default PROTGAMMAWAG, PhylogenomicPipeline2.java:248-250); threads/processes are accepted
-and ignored (the GPU engine needs no -T).  Not mirrored (out of scope): parsimony
-bootstrap (-Y), nucleotide (-gtr -nt).
+and ignored (the GPU engine needs no -T).  The parsimony bootstrap (-Y -N) and buildConcatenatedTree
+(PhylogenomicPipeline2.java:836-890) go through pml_bootstrap2.  Not mirrored (out of scope,
+SURVEY.md 8a): nucleotide (-gtr -nt).
 """
 import logging
 import os
@@ -114,6 +115,7 @@ class RAxMLRunner:
         self.algorithm = 0            # 1 = parsimony only, 2 = parsimony + ML lengths (RAxMLRunner.java:28-29)
         self.parsimonyTree = None
         self.parsimonyWithBLTree = None
+        self.bootstrapTrees = None    # the replicate trees of a parsimony bootstrap (-Y -N)
         self.bestTreeWithSupports = None
         self.seed = 12345
         self.searchSchedule = None    # None: one fixed radius (spr_radius); "raxml": pml_search2's schedule, radius determined per gene
@@ -185,8 +187,15 @@ class RAxMLRunner:
                     self.perSiteLLs.append(r["site_lnl"])
                 return
             if self.algorithm in (1, 2):
-                if self.bootstrapReps:
-                    raise ValueError("parsimony bootstrap (-Y -N) is not on the GPU path")
+                if self.bootstrapReps:                                         # -Y -N reps (RAxMLRunner.java:134-137): pml_bootstrap2
+                    method = engine.TREE_PARSIMONY if self.algorithm == 1 else engine.TREE_PARSIMONY_BL
+                    r = ctx.bootstrap2([gene], reps=self.bootstrapReps, seed=self.seed, method=method, parsimony_radius=20, **mdl)
+                    self.bootstrapTrees = r["replicates"]
+                    if self.algorithm == 1:
+                        self.parsimonyTree = r["newick"]
+                    else:
+                        self.parsimonyWithBLTree, self.lnl, self.alpha = r["newick"], r["lnl"], r["alpha"]
+                    return
                 p = ctx.parsimony([gene], seed=self.seed)[0]                  # -f d -y
                 self.parsimonyTree = p["newick"]
                 if self.algorithm == 2:                                        # -f e -t RAxML_parsimonyTree.<run>
@@ -740,6 +749,26 @@ class PhylogeneticTreeBuilder:
             # buildConcatenatedTreeWithGeneWiseJackKnifeSupport), but this dispatch keeps refusing it: callers and the mirror test
             # (tests/test_tree_builder_mirror.py::test_dispatch_and_errors_cpu) rely on the refusal, so it is not changed here
             raise ValueError("tree building method %r is outside the GPU path (ml, FastTree, parsimony, parsimony_bl)" % self.treeBuildingMethod)
+
+
+def buildConcatenatedTree(genes, bootstraps=100, concatenatedTreeMethod=ML, mlMatrix="PROTGAMMAWAG", ctx=None, seed=1, details=False):
+    """PhylogenomicPipeline2.buildConcatenatedTree (:836-890; reached from :395-402 with `-concatenated true` and no
+    `-gene_wise_jackknife`, bootstraps = support_reps, default 100) as one engine call (pml_bootstrap2): the tree of the
+    concatenation of `genes` under "ml" (`-f a -x -N`), "parsimony" or "parsimony_bl" (`-Y -N`), with the column bootstrap's
+    percent supports when bootstraps > 0.  The genes are encoded once and every replicate is built on the device.  "FastTree"
+    and "nj" are refused: their bootstraps are not built.  -> the tree string (the reference's return value), or with details
+    the dict of Context.bootstrap2."""
+    if concatenatedTreeMethod in (FAST_TREE, NEIGHBOR_JOINING):
+        raise ValueError("concatenated tree method %r has no bootstrap on the GPU path (ml, parsimony, parsimony_bl)" % concatenatedTreeMethod)
+    if concatenatedTreeMethod not in (ML, PARSIMONY, PARSIMONY_BL):
+        raise ValueError("concatenated tree method %r is not built here (ml, parsimony, parsimony_bl)" % concatenatedTreeMethod)
+    mdl = _model_from_matrix(mlMatrix, ctx)                         # an unbuilt model name is refused before any device work
+    ctx = ctx or default_context()
+    pairs = [g.as_gene() if hasattr(g, "as_gene") else g for g in genes]
+    methods = {ML: engine.TREE_ML, PARSIMONY: engine.TREE_PARSIMONY, PARSIMONY_BL: engine.TREE_PARSIMONY_BL}
+    r = ctx.bootstrap2(pairs, reps=int(bootstraps), seed=seed, method=methods[concatenatedTreeMethod], spr_radius=5, parsimony_radius=20,
+                       pi_mode=mdl["pi_mode"], ncat=mdl["ncat"])
+    return r if details else r["newick"]
 
 
 def buildConcatenatedTreeWithGeneWiseJackKnifeSupport(genes, reps=100, supportTreeMethod=FAST_TREE, mlMatrix="PROTGAMMAWAG",

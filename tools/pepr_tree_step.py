@@ -9,7 +9,7 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
                          [--full-tree-method ml|parsimony|parsimony_bl|nj] [--support-tree-method ml|FastTree|parsimony|nj]
-                         [-uniform_trim] [-congruence_filter] [-trim_percent 0.1] [-gene_steps [REPS ALPHA]]
+                         [-uniform_trim] [-congruence_filter] [-trim_percent 0.1] [-gene_steps [REPS ALPHA]] [-concatenated]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
                   PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
@@ -39,6 +39,11 @@ usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-se
                   the other genes' columns, the ceil(REPS * ALPHA)-th largest; -1 when the others hold fewer than three times the
                   gene's columns) with n_ge, the samples at or above the gene's own total.  Defaults 1000 and 0.05; the draws take
                   -seed.  Writes <run>.steps.tsv: gene, columns, steps, beyond, ratio, threshold, n_ge -- one row per gene
+-concatenated     PEPR's `-concatenated true` without -gene_wise_jackknife (PhylogenomicPipeline2.java:395-402, buildConcatenatedTree
+                  :836-890): ONE tree of the concatenation under --full-tree-method ml | parsimony | parsimony_bl and --matrix, with
+                  the column bootstrap's percent supports from -support_reps replicates (`-f a -x -N`, `-Y -N`; include/peprml.h
+                  pml_bootstrap2).  The genes are encoded once; every replicate is built on the device.  <run>.sup holds the
+                  replicate trees.  FastTree and nj are refused
 Without these flags the step runs as it always did (pml_jackknife: PROTGAMMAWAG, rule 0).
 """
 import glob
@@ -121,7 +126,15 @@ def main(argv):
         print("Discarded: %d\tKept: %d" % (len(files) - len(genes), len(genes)))
         files = [f for f, k in zip(files, r["keep"]) if k]
     t0 = time.time()
-    if {"full_tree_method", "support_tree_method"} & set(args):
+    if args.get("concatenated", "false").lower() == "true":
+        from pepr_amd import tree_builder
+        if {"support_tree_method", "support_matrix", "support_rule"} & set(args):
+            raise SystemExit("-concatenated builds one tree with column-bootstrap supports: --support-tree-method, --support-matrix and "
+                             "--support-rule belong to the gene-wise jackknife")
+        r = tree_builder.buildConcatenatedTree(genes, reps, args.get("full_tree_method", tree_builder.ML), args.get("matrix", "PROTGAMMAWAG"),
+                                               ctx=ctx, seed=int(args.get("seed", 1)), details=True)
+        r["support_trees"] = r["replicates"]
+    elif {"full_tree_method", "support_tree_method"} & set(args):
         from pepr_amd import tree_builder
         if "support_matrix" in args:
             raise SystemExit("--support-matrix does not go with --full-tree-method / --support-tree-method: ml support trees take --matrix, "
