@@ -840,7 +840,8 @@ static int gamma20_chunk(pml_ctx *ctx, int n, const pml_alignment *alns, const c
         for (int i = 0; i < n && !rc; ++i) {
             const Gene &G = b->b.genes[i];
             Tree T = G.tree;
-            for (auto &l : T.len) for (double &x : l) x *= rs[i];
+            const double scale = rs[i];
+            T.map_len([scale](double x) { return x * scale; });
             out[i].lnl = lnl[i]; out[i].alpha = al[i]; out[i].tree_length = T.length(); out[i].npatterns = G.aln.npat; out[i].nsites = G.aln.nsites;
             out[i].newick = dup_string(T.newick(G.aln.names, 10));
             if (!out[i].newick) rc = ctx->c.fail(PML_ENOMEM, "host allocation failed");

@@ -1088,7 +1088,7 @@ int Batch::optimize(bool opt_alpha_flag, double eps, double *lnl, const std::vec
     for (int g = 0; g < n; ++g) {
         if (!active[g]) continue;
         Tree &T = genes[g].tree;
-        for (auto &l : T.len) for (double &x : l) if (x < TMIN) x = TMIN;
+        T.map_len([](double x) { return x < TMIN ? TMIN : x; });
         invalidate_all(g);
     }
     const std::vector<char> initial(active);

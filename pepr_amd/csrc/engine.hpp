@@ -217,7 +217,10 @@ struct Batch {
         bool stored = false;                       // recorded with every CLV written (the traversal a search runs) instead of OPF_NO_STORE
         std::vector<ReqSrc> src; std::vector<std::pair<int, int>> outs;
         std::vector<unsigned> rates_seen;          // per gene: rates_epoch the descriptors carry
-        std::vector<std::vector<std::array<double, 3>>> len_seen;   // per gene: the branch lengths the descriptors carry (empty: not compared yet)
+        std::vector<unsigned long long> len_seen;  // per gene: Tree::len_stamp of the branch lengths the descriptors carry (0: not compared yet)
+        // PML_CHECK_LEN_STAMP=1 when the plan was recorded (test hook): every replay also compares the lengths as bytes against
+        // this copy per gene and fails if they differ under an unchanged stamp
+        bool check_len = false; std::vector<std::vector<std::array<double, 3>>> len_copy;
         std::vector<char> moved;                   // replay scratch, per gene: bit 0 lengths, bit 1 rates differ from the descriptors
         bool per_gene = false;                     // one evaluation per gene in gene order: the reductions write d_plan_lnl
     } plan;

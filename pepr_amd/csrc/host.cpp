@@ -2,6 +2,7 @@
 #include "host.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cmath>
 #include <cstdio>
@@ -13,6 +14,9 @@
 #include <unordered_map>
 
 namespace pml {
+
+// trees are built and changed on several host threads (Batch::create, the groups of a search call): one counter for all
+unsigned long long next_len_stamp() { static std::atomic<unsigned long long> clock{0}; return ++clock; }
 
 // ------------------------------------------------------------------------------------------
 // WAG (Whelan & Goldman 2001), amino-acid order ARNDCQEGHILKMFPSTWYV; lower triangle by rows.
@@ -342,7 +346,7 @@ struct Builder {
     void connect(int a, int b, double l) {
         int k = 0; while (k < 3 && T.nbr[a][k] >= 0) ++k;
         int m = 0; while (m < 3 && T.nbr[b][m] >= 0) ++m;
-        T.nbr[a][k] = b; T.len[a][k] = l; T.nbr[b][m] = a; T.len[b][m] = l;
+        T.nbr[a][k] = b; T.put_len(a, k, l); T.nbr[b][m] = a; T.put_len(b, m, l);
     }
     // returns node id of the (binary-resolved) subtree rooted at parsed node r; extra receives the
     // length accumulated through unary nodes
@@ -369,7 +373,7 @@ static bool build_tree(Parser &P, int root, const std::vector<int> &tipid, int n
     if (ntax < 3) { err = "need at least 3 taxa"; return false; }
     out.ntax = ntax;
     out.nbr.assign(2 * ntax - 2, {-1, -1, -1});
-    out.len.assign(2 * ntax - 2, {0.0, 0.0, 0.0});
+    out.reset_len(2 * ntax - 2);
     while (P.nodes[root].kids.size() == 1) root = P.nodes[root].kids[0];
     Builder B{P, out, tipid, ntax};
     auto &kids = P.nodes[root].kids;
@@ -388,7 +392,7 @@ static bool build_tree(Parser &P, int root, const std::vector<int> &tipid, int n
         B.connect(id, cur, curl); B.connect(id, ids[ids.size() - 2], ls[ids.size() - 2]); B.connect(id, ids.back(), ls.back());
     }
     if (B.next_inner != 2 * ntax - 2) { err = "internal: node count mismatch"; return false; }
-    for (auto &l : out.len) for (double &x : l) { if (!(x >= 0)) x = 0; if (x > TMAX) x = TMAX; }
+    out.map_len([](double x) { if (!(x >= 0)) x = 0; return x > TMAX ? TMAX : x; });
     return true;
 }
 
@@ -830,11 +834,11 @@ Tree nj_from_counts(int n, const std::vector<int64_t> &cmpc, const std::vector<i
             if (cmp > 0) { const double pd = diff / cmp; d = -std::log(std::max(1.0 - pd - 0.2 * pd * pd, 0.05)); }
             D[(size_t)i * N + j] = D[(size_t)j * N + i] = d;
         }
-    Tree T; T.ntax = n; T.nbr.assign(N, {-1, -1, -1}); T.len.assign(N, {0.0, 0.0, 0.0});
+    Tree T; T.ntax = n; T.nbr.assign(N, {-1, -1, -1}); T.reset_len(N);
     auto connect = [&](int x, int y, double l) {
         l = std::min(std::max(l, TMIN), TMAX);
         int k = 0; while (T.nbr[x][k] >= 0) ++k; int m = 0; while (T.nbr[y][m] >= 0) ++m;
-        T.nbr[x][k] = y; T.len[x][k] = l; T.nbr[y][m] = x; T.len[y][m] = l;
+        T.nbr[x][k] = y; T.put_len(x, k, l); T.nbr[y][m] = x; T.put_len(y, m, l);
     };
     std::vector<int> act(n); for (int i = 0; i < n; ++i) act[i] = i;
     int next = n;

@@ -38,13 +38,33 @@ void gamma_rates(double alpha, int K, double *rates);
 
 int aa_code(int ch);                 // 0..19, 20 = B, 21 = Z, 22 = gap/unknown
 
+// A tree's branch lengths: everybody reads them, only Tree's writers below change them, and every change gives the tree a new
+// LENGTH STAMP (Tree::len_stamp), unique in the process.  A copy of a tree carries the stamp of the lengths it copies, so two
+// trees with equal stamps have equal lengths -- after an assignment, an undo from a backup or a replaced tree as well.  A
+// recorded scoring plan compares stamps instead of bytes (Batch::replay_plan).  Code that writes `T.len[v][k] = x` does not compile.
+unsigned long long next_len_stamp();           // host.cpp: never 0, never repeated
+class BranchLengths {
+    std::vector<std::array<double, 3>> v;
+    friend struct Tree;
+public:
+    const std::array<double, 3> &operator[](size_t i) const { return v[i]; }
+    size_t size() const { return v.size(); }
+    std::vector<std::array<double, 3>>::const_iterator begin() const { return v.begin(); }
+    std::vector<std::array<double, 3>>::const_iterator end() const { return v.end(); }
+    const std::vector<std::array<double, 3>> &values() const { return v; }
+};
 struct Tree {
     int ntax = 0;
     std::vector<std::array<int, 3>> nbr;       // -1 = unused (tips use slot 0 only)
-    std::vector<std::array<double, 3>> len;
+    BranchLengths len;
+    unsigned long long len_stamp = 0;          // 0: no lengths yet
     int nnodes() const { return (int)nbr.size(); }
     int slot(int v, int w) const { for (int k = 0; k < 3; ++k) if (nbr[v][k] == w) return k; return -1; }
-    void set_len(int u, int v, double l) { len[u][slot(u, v)] = l; len[v][slot(v, u)] = l; }
+    // the writers of len: one directed slot, all slots cleared, all slots through f, both directions of a branch
+    void put_len(int v, int k, double l) { len.v[v][k] = l; len_stamp = next_len_stamp(); }
+    void reset_len(size_t nnodes) { len.v.assign(nnodes, {0.0, 0.0, 0.0}); len_stamp = next_len_stamp(); }
+    template <class F> void map_len(F f) { for (auto &l : len.v) for (double &x : l) x = f(x); len_stamp = next_len_stamp(); }
+    void set_len(int u, int v, double l) { put_len(u, slot(u, v), l); put_len(v, slot(v, u), l); }
     double length() const;
     // names[i] is the label of tip i; returns false and fills err on failure
     static bool parse(const char *newick, const std::vector<std::string> &names, Tree &out, std::string &err);

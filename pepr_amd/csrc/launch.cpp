@@ -632,7 +632,9 @@ struct LaunchBuilder {
             for (size_t g_ = 0; g_ < L.neval; ++g_) pred[g_].out = b.d_plan_lnl + g_;
             HIPCHK(hipMemcpyAsync((char *)P.d + L.o_red, pred, L.neval * sizeof(ReduceReq), hipMemcpyHostToDevice, ctx->stream));
         }
-        P.len_seen.assign(genes.size(), {});
+        P.len_seen.assign(genes.size(), 0);
+        P.check_len = std::getenv("PML_CHECK_LEN_STAMP") != nullptr;
+        P.len_copy.assign(P.check_len ? genes.size() : 0, {});
         P.set = L; P.stored = b.record_stored;
         P.rates_seen.resize(genes.size()); for (size_t g_ = 0; g_ < genes.size(); ++g_) P.rates_seen[g_] = genes[g_].rates_epoch;
         P.src = sc.last_src; P.outs.clear();
@@ -673,17 +675,25 @@ int Batch::replay_plan(double *lnl) {
     HIPCHK(hipSetDevice(ctx->device));
     PmatReq *hreq = (PmatReq *)((char *)P.h + P.set.o_req);
     // Only genes whose rates (alpha) or branch lengths moved since the descriptors were last refreshed have their requests
-    // visited: the device waits while this runs, and a step with nothing changed goes straight to the launches.  Lengths are
-    // compared as bytes against a copy per gene (2.4 KB for 50 taxa), whoever wrote them.
+    // visited: the device waits while this runs, and a step with nothing changed goes straight to the launches.  What tells is
+    // the gene's rates epoch and its tree's length stamp (host.hpp: every writer of Tree::len renews it, a copy carries it),
+    // two integer compares per gene.  (Until r06 the lengths were compared as bytes against a copy per gene, 2.4 KB for 50
+    // taxa: 7 us of a C3 step with the device idle, profiles/r06_ab_step_path.txt.)
     std::vector<char> &moved = P.moved;
     moved.assign(genes.size(), 0);
     bool any_moved = false;
     for (size_t g = 0; g < genes.size(); ++g) {
         const Gene &G = genes[g];
-        auto &seen = P.len_seen[g];
         if (P.rates_seen[g] != G.rates_epoch) { moved[g] = 3; P.rates_seen[g] = G.rates_epoch; }
-        if (seen.size() != G.tree.len.size() || std::memcmp(seen.data(), G.tree.len.data(), seen.size() * sizeof seen[0]) != 0) { moved[g] |= 1; seen = G.tree.len; }
+        if (P.len_seen[g] != G.tree.len_stamp) { moved[g] |= 1; P.len_seen[g] = G.tree.len_stamp; }
         any_moved = any_moved || moved[g];
+    }
+    if (P.check_len) for (size_t g = 0; g < genes.size(); ++g) {       // test hook: the byte compare, beside the stamps
+        const auto &now = genes[g].tree.len.values();
+        auto &was = P.len_copy[g];
+        if (!(moved[g] & 1) && (was.size() != now.size() || std::memcmp(was.data(), now.data(), now.size() * sizeof now[0]) != 0))
+            return ctx->fail(-5, "internal: branch lengths of gene " + std::to_string(g) + " changed under an unchanged length stamp");
+        if (moved[g] & 1) was = now;
     }
     bool changed = false;                       // lengths and rates already on the device are not uploaded again
     if (any_moved) for (size_t i = 0; i < P.set.nreq; ++i) {

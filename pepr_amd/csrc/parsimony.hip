@@ -299,7 +299,7 @@ static int parsimony_core(Ctx *ctx, std::vector<PGene> &G, const std::vector<uns
         for (int i = 0; i < nt; ++i) pg.order[i] = i;
         if (seeds[g]) { uint64_t s = seeds[g]; for (int i = nt - 1; i >= 1; --i) std::swap(pg.order[i], pg.order[(int)(splitmix(s) % (uint64_t)(i + 1))]); }
         Tree &t = pg.tree; t.ntax = nt;
-        t.nbr.assign(2 * nt - 2, {-1, -1, -1}); t.len.assign(2 * nt - 2, {0.1, 0.1, 0.1});
+        t.nbr.assign(2 * nt - 2, {-1, -1, -1}); t.reset_len(2 * nt - 2); t.map_len([](double) { return 0.1; });
         for (int k = 0; k < 3; ++k) { t.nbr[nt][k] = pg.order[k]; t.nbr[pg.order[k]][0] = nt; }
     }
     std::vector<PGene *> owner; std::vector<std::vector<FOp>> ops_of; std::vector<int> nscores; std::vector<std::vector<int>> scores;

@@ -39,7 +39,7 @@ void others(const Tree &T, int v, int excl, int out[2], double len[2]) {
 void tree_swap(Tree &T, int u, int x, int v, int y) {
     const int ku = T.slot(u, x), kv = T.slot(v, y), kx = T.slot(x, u), ky = T.slot(y, v);
     const double lx = T.len[u][ku], ly = T.len[v][kv];
-    T.nbr[u][ku] = y; T.len[u][ku] = ly; T.nbr[v][kv] = x; T.len[v][kv] = lx;
+    T.nbr[u][ku] = y; T.put_len(u, ku, ly); T.nbr[v][kv] = x; T.put_len(v, kv, lx);
     T.nbr[x][kx] = v; T.nbr[y][ky] = u;
 }
 void nni_apply(Tree &T, int u, int v, int alt, double tnew) {
@@ -376,10 +376,10 @@ void spr_apply(Tree &T, int p, int x, int y, int g, int h) {
     const int kx = T.slot(p, x), ky = T.slot(p, y);
     const double tx = T.len[p][kx], ty = T.len[p][ky], tgh = T.len[g][T.slot(g, h)];
     const int sx = T.slot(x, p), sy = T.slot(y, p);
-    T.nbr[x][sx] = y; T.len[x][sx] = tx + ty; T.nbr[y][sy] = x; T.len[y][sy] = tx + ty;
+    T.nbr[x][sx] = y; T.put_len(x, sx, tx + ty); T.nbr[y][sy] = x; T.put_len(y, sy, tx + ty);
     const int sg = T.slot(g, h), sh = T.slot(h, g);
-    T.nbr[g][sg] = p; T.len[g][sg] = 0.5 * tgh; T.nbr[h][sh] = p; T.len[h][sh] = 0.5 * tgh;
-    T.nbr[p][kx] = g; T.len[p][kx] = 0.5 * tgh; T.nbr[p][ky] = h; T.len[p][ky] = 0.5 * tgh;
+    T.nbr[g][sg] = p; T.put_len(g, sg, 0.5 * tgh); T.nbr[h][sh] = p; T.put_len(h, sh, 0.5 * tgh);
+    T.nbr[p][kx] = g; T.put_len(p, kx, 0.5 * tgh); T.nbr[p][ky] = h; T.put_len(p, ky, 0.5 * tgh);
 }
 // the prune (p, ks) of gene g with its candidates as launchable units
 void prune_units(const Batch &B, int g, int p, int ks, int rmin, int rmax, std::vector<SprCandidate> &cands, Prune &P) {
