@@ -771,6 +771,59 @@ int  pml_trim_column_flags_host(const pml_alignment *gene, unsigned char *flags_
  * total_ms[0] = k_colclass, [1] = k_colgather, [2] = the host-to-device copies of the genes' bytes.  Never reset. */
 int  pml_trim_stats(pml_ctx *ctx, long long *class_launches, long long *gather_launches, double *total_ms /* [3] */);
 
+/* The reference's `-gblocks_trim` (PhyloPipeline.java:1121 sets it on the default track): MSATrimmer.trim (MSATrimmer.java:41-126) runs
+ * `Gblocks <file> -o -b1=ceil(0.8 n) -b3=8 -b5=h` on every gene before -uniform_trim, the congruence filter and the trees.  Here the
+ * block selection runs on the device (gblocks.hip).  PARITY WITH THE Gblocks BINARY IS UNPINNED: the reference holds no source of it
+ * and the bundled 32-bit binary does not start, so the rule below is the published one (Castresana 2000 and the program's
+ * documentation) and the tests pin the device against an independent restatement of this text.  Deliberate difference: residues are
+ * counted by identity; the binary's similarity-matrix option, which its documentation describes as on by default for proteins, is
+ * not applied (its matrix is not in the reference).
+ *   A gene has n rows and L columns.  Bytes are compared by identity; '-' is the only gap byte, '?', 'X' and everything else are
+ *   residues.  Parameters b1 <= b2 (conserved / flank thresholds), b3 (longest run of non-conserved columns tolerated), b4 (minimum
+ *   block length), b0 (minimum length of an initial block), gaps.  A field that is 0 takes PEPR's value: b1 = (int)ceil(n * 0.8) in
+ *   double (MSATrimmer.java:94-95), b2 = max(b1, 85 n / 100) in integer division (the program's documented default of 85 %; its
+ *   rounding is unpinned), b3 = 8, b4 = b0 = 10, gaps = PML_GBLOCKS_GAPS_HALF.  Anything outside n / 2 < b1 <= b2 <= n, b3 >= 0,
+ *   b4 >= 2, b0 >= 2 is PML_EINVAL.
+ *   Per column, gaps(c) = its '-' bytes, top(c) = the largest count of one non-gap byte.  The column is a gap position under NONE iff
+ *   gaps(c) > 0, under HALF iff 2 gaps(c) >= n, under ALL never.  Its class is 0 (non-conserved) if it is a gap position or
+ *   top < b1, 2 (highly conserved) if top >= b2, else 1 (conserved).
+ *   Every column starts selected; a block is a maximal run of selected columns.
+ *   1. every maximal run of class-0 columns longer than b3 is deselected;
+ *   2. in every block columns are deselected from each end until a class-2 column is reached (a block without one vanishes);
+ *   3. every block shorter than b0 is deselected;
+ *   4. inside the blocks every gap position is deselected, and every class-0 column joined to a gap position by an unbroken run of
+ *      selected class-0 columns;
+ *   5. every block shorter than b4 is deselected.
+ * Kept columns keep their order, rows and names are untouched, a gene may end with 0 columns.  pml_gblocks_trim fills the
+ * trim result of pml_trim_columns, gap_or_missing (the '-' and '?' cells of the untrimmed gene) included, and sub-batches under the HBM budget as
+ * pml_trim_columns does (PML_HBM_BUDGET_MB; a single gene that does not fit is PML_ENOMEM with the size).  Selection, the kept
+ * columns' prefix and the gather run on the device without a host step in between. */
+enum { PML_GBLOCKS_GAPS_NONE = 1, PML_GBLOCKS_GAPS_HALF = 2, PML_GBLOCKS_GAPS_ALL = 3 };
+typedef struct { int b1, b2, b3, b4, b0, gaps; } pml_gblocks_params;
+/* host-only: PEPR's parameters for a gene of ntax rows */
+int  pml_gblocks_defaults(int ntax, pml_gblocks_params *out);
+int  pml_gblocks_trim(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_gblocks_params *params /* NULL = PEPR's */,
+                      pml_trim_result *result);
+/* test door: one byte per column as k_gbclass and k_gbselect wrote it: bits 0-1 = class, bit 2 = gap position, bit 4 = selected
+ * after step 1, bit 5 = after steps 2 and 3, bit 6 = after step 4, bit 7 = kept.  flags_out: gene->nsites bytes */
+int  pml_debug_gblocks_flags(pml_ctx *ctx, const pml_alignment *gene, const pml_gblocks_params *params, unsigned char *flags_out);
+/* host-only, needs no context: the same bytes from the same functions (csrc/gblocks.hpp) with sequential scans */
+int  pml_gblocks_flags_host(const pml_alignment *gene, const pml_gblocks_params *params, unsigned char *flags_out);
+/* the columns k_gbselect scans at a time (tests place their cases across this boundary) */
+int  pml_gblocks_chunk(void);
+/* k_gbclass and k_gbselect launches on this context so far and, with cfg.profile = 1, summed HIP-event times in ms:
+ * total_ms[0] = k_gbclass, [1] = k_gbselect, [2] = the host-to-device copies.  The gather counts in pml_trim_stats.  Never reset. */
+int  pml_gblocks_stats(pml_ctx *ctx, long long *class_launches, long long *select_launches, double *total_ms /* [3] */);
+/* The trimming stages in the reference's order (PhylogenomicPipeline2.getAlignment :737-806) in one resident call with one upload:
+ * Gblocks (use_gblocks != 0; gb as for pml_gblocks_trim), then the column filter (mode, -1 = none), then the congruence filter
+ * (trim_percent, 0 = none; keep_out is needed then).  Each stage reads the matrices the stage before left in HBM.  Equals
+ * pml_gblocks_trim, pml_trim_columns and pml_congruence_filter run one after the other on the returned text, field for field.  A
+ * gene that a stage empties while another stage follows is PML_EPARSE and names gene and stage.  All genes are resident together
+ * (PML_ENOMEM otherwise); no stage at all is PML_EINVAL; each result pointer may be NULL. */
+int  pml_trim_pipeline(pml_ctx *ctx, int ngenes, const pml_alignment *genes, const pml_gblocks_params *gb, int use_gblocks, int mode,
+                       double trim_percent, int *keep_out, pml_trim_result *gb_result, pml_trim_result *trim_result,
+                       pml_congruence_result *congruence_result);
+
 /* The gene homoplasy test of ConcatenatedSequenceAlignment.java:65-425: per-column parsimony steps of the concatenation on a tree,
  * the least steps a column can take, per-gene totals, and for every gene a randomisation threshold (genesteps.hip).  In the
  * reference this is dead code: its one input, setStepsPerSite (SequenceAlignment.java:1033), has no caller, because neither RAxML

@@ -33,6 +33,8 @@ SYMBOLS = [
     "pml_debug_tree_pair_sums",
     "pml_trim_columns", "pml_trim_result_free", "pml_trim_congruence_filter", "pml_debug_column_flags", "pml_trim_column_flags_host",
     "pml_trim_stats",
+    "pml_gblocks_defaults", "pml_gblocks_trim", "pml_debug_gblocks_flags", "pml_gblocks_flags_host", "pml_gblocks_chunk", "pml_gblocks_stats",
+    "pml_trim_pipeline",
     "pml_gene_steps", "pml_gene_steps_result_free", "pml_step_thresholds", "pml_step_draws_host", "pml_debug_step_replicates",
     "pml_gene_steps_stats",
     "pml_bootstrap2", "pml_boot_draws_host", "pml_boot_tile", "pml_debug_boot_replicate", "pml_boot_stats",
@@ -159,6 +161,10 @@ class TrimResult(C.Structure):
     _ip = C.POINTER(C.c_int)
     _fields_ = [("ngenes", C.c_int), ("ntax", _ip), ("ncols", _ip), ("nkept", _ip), ("kept_cols", C.POINTER(_ip)),
                 ("rows", C.POINTER(C.POINTER(C.c_void_p))), ("gap_or_missing", C.POINTER(C.c_longlong))]
+
+
+class GblocksParams(C.Structure):
+    _fields_ = [("b1", C.c_int), ("b2", C.c_int), ("b3", C.c_int), ("b4", C.c_int), ("b0", C.c_int), ("gaps", C.c_int)]
 
 
 class GeneStepsResult(C.Structure):
@@ -306,6 +312,14 @@ def load():
     L.pml_debug_column_flags.argtypes = [vp, ap, C.POINTER(C.c_ubyte)]
     L.pml_trim_column_flags_host.argtypes = [ap, C.POINTER(C.c_ubyte)]
     L.pml_trim_stats.argtypes = [vp, lp, lp, dp]
+    gbp, ubp = C.POINTER(GblocksParams), C.POINTER(C.c_ubyte)
+    L.pml_gblocks_defaults.argtypes = [C.c_int, gbp]
+    L.pml_gblocks_trim.argtypes = [vp, C.c_int, ap, gbp, trp2]
+    L.pml_debug_gblocks_flags.argtypes = [vp, ap, gbp, ubp]
+    L.pml_gblocks_flags_host.argtypes = [ap, gbp, ubp]
+    L.pml_gblocks_chunk.argtypes = []
+    L.pml_gblocks_stats.argtypes = [vp, lp, lp, dp]
+    L.pml_trim_pipeline.argtypes = [vp, C.c_int, ap, gbp, C.c_int, C.c_int, C.c_double, ip, trp2, trp2, crp]
     gsp, stp = C.POINTER(GeneStepsResult), C.POINTER(StepThresholdOpts)
     L.pml_gene_steps.argtypes = [vp, C.c_int, ap, C.c_char_p, gsp]
     L.pml_gene_steps_result_free.argtypes = [gsp]

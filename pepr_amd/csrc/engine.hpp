@@ -47,6 +47,7 @@ struct Ctx {
     long long newton_giveups = 0, newton_reissued = 0, newton_seq_launches = 0;   // k_newton fallback statistics (pml_newton_fallbacks)
     long long fitch_tips_launches = 0, fitch_launches = 0;      // k_fitch_tips and k_fitch launches (pml_fitch_stats)
     long long colclass_launches = 0, colgather_launches = 0; double trim_ms[3] = {0, 0, 0};   // pml_trim_stats: k_colclass, k_colgather, the uploads
+    long long gbclass_launches = 0, gbselect_launches = 0; double gb_ms[3] = {0, 0, 0};       // pml_gblocks_stats: k_gbclass, k_gbselect, the uploads
     long long gs_launches[5] = {0, 0, 0, 0, 0}; double gs_ms[5] = {0, 0, 0, 0, 0};   // pml_gene_steps_stats: k_fitch_sitesteps, k_steps_expand, k_colminsteps, k_steps_resample, k_steps_table
     // pml_boot_stats: k_boot_count, k_boot_index, k_boot_gather, k_boot_pairs launches, (profile mode) their HIP-event times, and the
     // host wall time of the replicate builds (count .. NJ starts / tip rows)

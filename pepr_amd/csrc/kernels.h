@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gblocks.hpp"
 #include "treecmp.hpp"
 
 namespace pml {
@@ -240,6 +241,18 @@ void launch_colclass(const CgGene *genes, const int *tile_gene, const int *tile_
 struct TgGene { const uint8_t *in; uint8_t *out; const int *src_col; int ntax, nkept, ld_in, ld_out; };
 struct TgTile { int gene, chunk0, row0, pad; };
 void launch_colgather(const TgGene *genes, const TgTile *tiles, int ntiles, hipStream_t s);
+
+// Block trimming (gblocks.hip, rules in gblocks.hpp): the reference's `-gblocks_trim`.  Genes in the CgGene layout as above, plus
+// one GbGene each: the resolved parameters, src_col (ld ints, 16-byte aligned) and, for a gene of more than GB_LDS_COLS columns,
+// scratch (2 * ncols ints).
+// k_gbclass: tiles as k_colclass; flags[col_base + column] = gb_class's byte, gap_or_missing[gene] += its '-' and '?' cells
+// k_gbselect: one workgroup per gene: the five rounds on flags[col_base ..] (stage bits ORed in), then the kept columns' indices,
+// ascending, to src_col (the entries up to the next multiple of 16: -1) and their number to tg[gene].nkept, rounded up to 16 to
+// tg[gene].ld_out -- what k_colgather reads, so that it can follow without the host in between
+struct GbGene { int ntax, ncols; long long col_base; int *src_col; int *scratch; GbParams p; };
+void launch_gbclass(const CgGene *genes, const GbGene *gb, const int *tile_gene, const int *tile_first, int ntiles, uint8_t *flags,
+                    long long *gap_or_missing, hipStream_t s);
+void launch_gbselect(const GbGene *gb, int ngenes, uint8_t *flags, TgGene *tg, hipStream_t s);
 
 // The gene homoplasy test (genesteps.hip; rules in include/peprml.h, draw functions in genesteps.hpp).  A sub-batch's genes: raw
 // bytes in the CgGene layout (rows ld bytes apart) for k_colminsteps, site2pat for k_steps_expand; pat_off = the gene's first

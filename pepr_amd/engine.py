@@ -18,6 +18,8 @@ NJ_DISTANCE, NJ_SIMILARITY = 0, 1      # pml_nj_from_matrix matrix types (TreeBu
 NJ_TREE, NJ_TOPOLOGY = 0, 1            # getNJTreeString (lengths) / getNJTopology (the `-nj true` path)
 TREE_ML, TREE_PARSIMONY, TREE_PARSIMONY_BL = 0, 1, 2      # pml_jackknife3 tree-building methods (PML_TREE_*)
 TRIM_UNIFORM, TRIM_GAP_UNIFORM, TRIM_TOPOLOGICAL = 0, 1, 2     # pml_trim_columns modes (PML_TRIM_*): MSATrimmer's three filters
+GBLOCKS_GAPS_NONE, GBLOCKS_GAPS_HALF, GBLOCKS_GAPS_ALL = 1, 2, 3     # pml_gblocks_params.gaps (PML_GBLOCKS_GAPS_*); 0 = PEPR's (HALF)
+GB_CLASS, GB_GAP_POS, GB_SEL1, GB_SEL3, GB_SEL4, GB_KEPT = 3, 4, 16, 32, 64, 128      # the bits of a debug_gblocks_flags byte
 STEPS_RAW, STEPS_BEYOND_MIN, STEPS_MIN_RATIO = 0, 1, 2     # pml_step_thresholds statistics (PML_STEPS_*)
 EINVAL = -1
 MODELDEV_DOUBLES = 20 + 400 + 400 + 20 + 400       # eval, U, Uinv, pi, Uinv transposed (kernels.h ModelDev)
@@ -47,6 +49,17 @@ def _aln_struct(names, rows, keep):
 def _raw_aln_struct(names, rows, keep):
     """as _aln_struct for the calls that compare bytes by identity: a str row is its latin-1 bytes (one byte per character)"""
     return _aln_struct(names, [r.encode("latin-1") if isinstance(r, str) else r for r in rows], keep)
+
+
+def _gblocks_params(params):
+    """None (PEPR's values) or a dict with any of b1, b2, b3, b4, b0, gaps (a missing or 0 field takes PEPR's value) -> the pointer
+    argument of the pml_gblocks_* calls"""
+    if params is None:
+        return None
+    unknown = set(params) - {"b1", "b2", "b3", "b4", "b0", "gaps"}
+    if unknown:
+        raise ValueError("unknown Gblocks parameters: %s" % sorted(unknown))
+    return C.byref(_lib.GblocksParams(*[int(params.get(k, 0)) for k in ("b1", "b2", "b3", "b4", "b0", "gaps")]))
 
 
 def _model(ncat=4, alpha=1.0, pi_mode=PI_RAXML_3DP):
@@ -707,6 +720,65 @@ class Context:
         self._check(self.L.pml_trim_stats(self.ptr, C.byref(a), C.byref(b), ms))
         return {"class_launches": a.value, "gather_launches": b.value, "class_ms": ms[0], "gather_ms": ms[1], "upload_ms": ms[2]}
 
+    # ---- the reference's `-gblocks_trim` (include/peprml.h pml_gblocks_trim) and the trimming stages as one call ----
+    def gblocks_trim(self, genes, params=None):
+        """MSATrimmer.trim's block selection on the device -> trim_columns' list.  params: None = PEPR's (b1 = ceil(0.8 n), b3 = 8,
+        half gaps), or a dict with any of b1, b2, b3, b4, b0, gaps.  The rule is the published one; parity with the Gblocks
+        binary is unpinned (include/peprml.h)."""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_raw_aln_struct(g[0], g[1], keep) for g in genes])
+        res = _lib.TrimResult()
+        self._check(self.L.pml_gblocks_trim(self.ptr, n, alns, _gblocks_params(params), C.byref(res)))
+        try:
+            return self._trim_result(res, genes)
+        finally:
+            self.L.pml_trim_result_free(C.byref(res))
+
+    def trim_pipeline(self, genes, gblocks=True, gblocks_params=None, mode=None, trim_percent=0):
+        """The trimming stages in the reference's order in one resident call (one upload): Gblocks (gblocks), then the column
+        filter (mode: None = none, or TRIM_*), then the congruence filter (trim_percent: 0 = none) -> {"gblocks": gblocks_trim's
+        list, "trimmed": trim_columns' list on the Gblocks stage's genes, plus congruence_filter's keys}, each only for a
+        stage that ran"""
+        keep = []
+        n = len(genes)
+        alns = (_lib.Alignment * n)(*[_raw_aln_struct(g[0], g[1], keep) for g in genes])
+        gres, tres, res = _lib.TrimResult(), _lib.TrimResult(), _lib.CongruenceResult()
+        flags = (C.c_int * n)()
+        self._check(self.L.pml_trim_pipeline(self.ptr, n, alns, _gblocks_params(gblocks_params), int(bool(gblocks)), -1 if mode is None else int(mode),
+                                             float(trim_percent), flags, C.byref(gres), C.byref(tres), C.byref(res)))
+        try:
+            out = {}
+            if trim_percent > 0:
+                out = self._congruence_result(res)
+                out.update(congruence_select(out["mean_cost"], trim_percent))          # idx and max_cost
+                out["keep"] = [bool(f) for f in flags]
+            if gblocks:
+                out["gblocks"] = self._trim_result(gres, genes)
+            if mode is not None:
+                out["trimmed"] = self._trim_result(tres, genes)
+        finally:
+            self.L.pml_congruence_result_free(C.byref(res))
+            self.L.pml_trim_result_free(C.byref(gres))
+            self.L.pml_trim_result_free(C.byref(tres))
+        return out
+
+    def debug_gblocks_flags(self, gene, params=None):
+        """Test door of k_gbclass and k_gbselect: one byte per column as the kernels wrote it (bits 0-1: class; bit 2: gap
+        position; bits 4 to 7: selected after step 1, after steps 2 and 3, after step 4, kept) -> uint8 array"""
+        keep = []
+        a = _raw_aln_struct(gene[0], gene[1], keep)
+        out = np.zeros(max(a.nsites, 1), dtype=np.uint8)
+        self._check(self.L.pml_debug_gblocks_flags(self.ptr, C.byref(a), _gblocks_params(params), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out[:a.nsites]
+
+    def gblocks_stats(self):
+        """k_gbclass / k_gbselect launches on this context so far and (profile mode) the summed HIP-event times in ms of the two
+        kernels and of the host-to-device copies; the gather counts in trim_stats"""
+        a, b, ms = C.c_longlong(), C.c_longlong(), (C.c_double * 3)()
+        self._check(self.L.pml_gblocks_stats(self.ptr, C.byref(a), C.byref(b), ms))
+        return {"class_launches": a.value, "select_launches": b.value, "class_ms": ms[0], "select_ms": ms[1], "upload_ms": ms[2]}
+
     # ---- the gene homoplasy test of ConcatenatedSequenceAlignment (include/peprml.h pml_gene_steps, pml_step_thresholds) ----
     def gene_steps(self, genes, newick):
         """Per-column Fitch steps of the concatenation of `genes` on `newick`, the least steps each column can take, and the
@@ -1349,6 +1421,31 @@ def trim_column_flags_host(gene):
     if rc:
         raise PmlError(rc)
     return out[:a.nsites]
+
+
+def gblocks_defaults(ntax):
+    """pml_gblocks_defaults: PEPR's Gblocks parameters for a gene of ntax rows -> {"b1", "b2", "b3", "b4", "b0", "gaps"}"""
+    p = _lib.GblocksParams()
+    rc = _lib.load().pml_gblocks_defaults(int(ntax), C.byref(p))
+    if rc:
+        raise PmlError(rc, "ntax %r" % (ntax,))
+    return {k: getattr(p, k) for k in ("b1", "b2", "b3", "b4", "b0", "gaps")}
+
+
+def gblocks_flags_host(gene, params=None):
+    """pml_gblocks_flags_host: Context.debug_gblocks_flags' bytes from the same functions on the host (no device)"""
+    keep = []
+    a = _raw_aln_struct(gene[0], gene[1], keep)
+    out = np.zeros(max(a.nsites, 1), dtype=np.uint8)
+    rc = _lib.load().pml_gblocks_flags_host(C.byref(a), _gblocks_params(params), out.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    if rc:
+        raise PmlError(rc)
+    return out[:a.nsites]
+
+
+def gblocks_chunk():
+    """the columns k_gbselect scans at a time"""
+    return _lib.load().pml_gblocks_chunk()
 
 
 def _gene_steps_struct(result):

@@ -362,10 +362,11 @@ def filterForCongruence(genes, percentileToRemove=0.1, ctx=None):
 
 
 class MSATrimmer:
-    """.../pepr/alignment/MSATrimmer.java's three column filters (:141-203, :205-253, :264-351) on the device
-    (Context.trim_columns; the rules are in include/peprml.h).  Each returns a new SequenceAlignment with the same taxa.  The
-    first two append "_ui" to the alignment's name (:197, :247: the Java concatenates, so a null name reads "null_ui"); the third
-    sets none.  Gblocks (trim) is not mirrored."""
+    """.../pepr/alignment/MSATrimmer.java's three column filters (:141-203, :205-253, :264-351) and its Gblocks step (trim, :41-126)
+    on the device (Context.trim_columns, Context.gblocks_trim; the rules are in include/peprml.h).  Each returns a new
+    SequenceAlignment with the same taxa.  The first two filters append "_ui" to the alignment's name (:197, :247: the Java
+    concatenates, so a null name reads "null_ui"); the third sets none; trim appends "_trim" (:46).  trim applies the published
+    block selection with PEPR's parameters; its parity with the Gblocks binary is unpinned (include/peprml.h)."""
 
     def __init__(self, ctx=None):
         self.ctx = ctx
@@ -375,6 +376,12 @@ class MSATrimmer:
         t = ctx.trim_columns([alignment.as_gene()], mode)[0]
         name = alignment.getName()
         return SequenceAlignment(alignment.getTaxa(), t["rows"], None if suffix is None else ("null" if name is None else name) + suffix)
+
+    def trim(self, alignment):
+        ctx = self.ctx or default_context()
+        t = ctx.gblocks_trim([alignment.as_gene()])[0]
+        name = alignment.getName()
+        return SequenceAlignment(alignment.getTaxa(), t["rows"], ("null" if name is None else name) + "_trim")
 
     def trimUniformativeColumns(self, alignment):
         return self._trim(alignment, engine.TRIM_GAP_UNIFORM, "_ui")

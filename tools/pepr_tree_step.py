@@ -9,7 +9,7 @@ buildConcatenatedTreeWithGeneWiseJackKnifeSupport writes (PhylogenomicPipeline2.
 usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-seed 1] [-device 0]
                          [--matrix NAME] [--support-matrix NAME] [--support-rule N]
                          [--full-tree-method ml|parsimony|parsimony_bl|nj] [--support-tree-method ml|FastTree|parsimony|nj]
-                         [-uniform_trim] [-congruence_filter] [-trim_percent 0.1] [-gene_steps [REPS ALPHA]] [-concatenated]
+                         [-gblocks_trim] [-uniform_trim] [-congruence_filter] [-trim_percent 0.1] [-gene_steps [REPS ALPHA]] [-concatenated]
 (flag style and names follow .../util/HandyConstants.java: run_name, support_reps)
 --matrix          RAxML model name of the full tree (what -matrix_eval chose; PROTGAMMAWAG, PROTGAMMAWAGF, PROTGAMMAGTR or
                   PROTGAMMA<NAME>[F] from <name>.dat in $PEPRML_MODEL_DIR, resolved as the raxmlHPC shim resolves -m)
@@ -33,6 +33,13 @@ usage: pepr_tree_step.py -run_name X -alignment_dir DIR [-support_reps 100] [-se
                   include/peprml.h (PML_TRIM_UNIFORM).  Writes <run>.trim.tsv: file, columns, kept -- one row per gene; a gene trimmed
                   to 0 columns is dropped with a message.  With -congruence_filter the genes are uploaded once and trimmed and
                   filtered in one call (pml_trim_congruence_filter)
+-gblocks_trim     PEPR's flag of the same name (the default track sets it, PhyloPipeline.java:1121): every gene goes through the block
+                  selection of MSATrimmer.trim (Gblocks -b1=ceil(0.8 n) -b3=8 -b5=h) first, before -uniform_trim and
+                  -congruence_filter, as PhylogenomicPipeline2.getAlignment orders them.  The rule is the published one, residues
+                  counted by identity; its parity with the Gblocks binary is unpinned (include/peprml.h pml_gblocks_trim).  Writes
+                  <run>.gblocks.tsv: file, columns, kept -- one row per gene; a gene trimmed to 0 columns is dropped with a message.
+                  With -uniform_trim and / or -congruence_filter the genes are uploaded once and all stages run in one call
+                  (pml_trim_pipeline)
 -gene_steps [REPS ALPHA]   the gene homoplasy test of ConcatenatedSequenceAlignment.java (include/peprml.h pml_gene_steps) on the full
                   tree just built: per gene the Fitch steps of its columns, the steps beyond the minimum, the steps-to-minimum
                   ratio, and the threshold of the Java's current rule (steps beyond the minimum, REPS samples with replacement from
@@ -94,9 +101,30 @@ def main(argv):
     ctx = engine.Context(int(args.get("device", 0)))
     filtering = args.get("congruence_filter", "false").lower() == "true"
     r = None
-    if args.get("uniform_trim", "false").lower() == "true":
-        trimmed = None
-        if filtering:                           # one upload: trimmed in HBM, the congruence stage runs on the trimmed matrices
+    uniform = args.get("uniform_trim", "false").lower() == "true"
+    trimmed = None
+    if args.get("gblocks_trim", "false").lower() == "true":
+        staged = None
+        if uniform or filtering:                # one upload: every stage reads the matrices the stage before left in HBM
+            try:
+                staged = ctx.trim_pipeline(genes, True, None, engine.TRIM_UNIFORM if uniform else None, float(args.get("trim_percent", 0.1)) if filtering else 0)
+            except engine.PmlError as e:        # a gene trimmed to nothing: it is dropped below and the steps run one after the other
+                if e.code != -2 or "no columns left" not in str(e):
+                    raise
+        blocks = staged["gblocks"] if staged else ctx.gblocks_trim(genes)
+        with open(args["run_name"] + ".gblocks.tsv", "w") as f:
+            f.write("file\tcolumns\tkept\n")
+            for name, t in zip(files, blocks):
+                f.write("%s\t%d\t%d\n" % (os.path.basename(name), t["ncols"], t["nkept"]))
+                if not t["nkept"]:
+                    print("dropping set %s: no column left after -gblocks_trim" % os.path.basename(name))
+        files = [f for f, t in zip(files, blocks) if t["nkept"]]
+        genes = [(t["names"], t["rows"]) for t in blocks if t["nkept"]]
+        if staged:
+            trimmed = staged.get("trimmed")
+            r = staged if filtering else None
+    if uniform:
+        if filtering and trimmed is None:       # one upload: trimmed in HBM, the congruence stage runs on the trimmed matrices
             try:
                 r = ctx.trim_congruence_filter(genes, engine.TRIM_UNIFORM, float(args.get("trim_percent", 0.1)))
                 trimmed = r["trimmed"]
