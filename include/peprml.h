@@ -957,6 +957,123 @@ void pml_tree_splits_free(pml_tree_splits *out);
 int  pml_debug_tree_pair_sums(pml_ctx *ctx, int ntrees, const char *const *newicks, int use_lengths, int npairs, const int *pairs /* [npairs][2] */,
                               long long *counts_out, double *sums_out);
 
+/* The reference's NeighborMasher (util/NeighborMasher.java): from a few ingroup genomes and a pool of candidate genomes it picks the
+ * ingroup's expansion and the outgroups and builds NJ trees of both from `mash sketch` / `mash dist` genome distances
+ * (TreeBuilder.getNJTreeString with TreeBuilder.DISTANCE = pml_nj_from_matrix, PML_NJ_DISTANCE, PML_NJ_TREE).  Here the sketches and
+ * the pair counts are computed on the device (mash.hip).  PARITY WITH THE mash BINARY IS UNPINNED: the reference holds neither a mash
+ * binary nor its source, so the rule below is the published one (Ondov et al. 2016 and the program's documentation) and the tests pin
+ * the device against an independent restatement of this text (tests/mash_ref.py).  Part of what is unpinned: NeighborMasher reads the
+ * distance from mash's text, which is taken to carry six significant digits; `digits` = 6 feeds strtod("%.6g") of the distance to
+ * the selection and to NJ, `digits` = 0 the double itself.  mash's p-value, -i, amino-acid alphabets and .msh files are not built.
+ *   windows    A genome is a list of records, each a byte string; 'a'..'z' read as upper case.  A window is k consecutive bytes of ONE
+ *              record, 1 <= k <= 32, valid iff all of them are in ACGT.  A record shorter than k gives none; an empty record is legal.
+ *   canonical  the smaller, as byte strings, of the window and its reverse complement; the window itself when they are equal (even
+ *              k, e.g. ACGT).
+ *   hash       h1 of MurmurHash3_x64_128 over the k canonical bytes with seed 42: c1 = 0x87c37b91114253d5, c2 = 0x4cf5ad432745937f,
+ *              h1 = h2 = seed; per 16-byte block, k1 and k2 read little-endian: k1 *= c1, k1 = rotl(k1, 31), k1 *= c2, h1 ^= k1,
+ *              h1 = rotl(h1, 27), h1 += h2, h1 = h1 * 5 + 0x52dce729; k2 *= c2, k2 = rotl(k2, 33), k2 *= c1, h2 ^= k2, h2 = rotl(h2, 31),
+ *              h2 += h1, h2 = h2 * 5 + 0x38495ab5.  Tail: bytes 8..14 little-endian into k2, mixed as above without the h2 rotation,
+ *              add and multiply; bytes 0..7 into k1 likewise.  Finish: h1 ^= len, h2 ^= len, h1 += h2, h2 += h1, h1 = fmix(h1),
+ *              h2 = fmix(h2), h1 += h2, h2 += h1; fmix(x): x ^= x >> 33, x *= 0xff51afd7ed558ccd, x ^= x >> 33,
+ *              x *= 0xc4ceb9fe1a85ec53, x ^= x >> 33.  For k <= 16 (4^k <= 2^32) only the low 32 bits of h1 are kept.
+ *              Check vectors: "The quick brown fox jumps over the lazy dog", seed 0: h1 = e34bbc7bbc071b6c, h2 = 7a433ca9c49a9347;
+ *              the empty string, seed 0: 0, 0; "ACGTACGTACGTACGTACGTA", seed 42: h1 = b4e9c495b633d387.
+ *   sketch     the ascending list of the min(s, D) smallest distinct values of a genome, D = its distinct values, s >= 1.  A genome
+ *              without a valid window has an empty sketch.
+ *   pair       for sketches a, b and size s:  i = j = common = denom = 0;  while denom < s and i < |a| and j < |b|:  a[i] < b[j]: i++;
+ *              b[j] < a[i]: j++;  else i++, j++, common++;  denom++.  Then, if denom < s: denom = min(s, denom + |a| - i + |b| - j).
+ *              common = the shared values among the s smallest of the union, denom = min(s, |union|): the device's two integers.
+ *   distance   on the host, in double: 0 if common == denom (two empty sketches included), else 1 if common == 0, else
+ *              min(1, -log(2 j / (1 + j)) / k) with j = common / denom.
+ * On the device a window that is not valid is marked with 2^64 - 1, so for k > 16 a valid window whose h1 IS 2^64 - 1 (one in 2^64)
+ * is dropped there and kept by the host doors: the one place where the two can differ.
+ * The Java half is source and pinned by reading, ties between equal distances excepted: the Java's HashSet / HashMap iteration
+ * leaves their order to the JVM, here they follow input order (after the stable sorts).
+ *   expandIngroup :281-324   a candidate's distance is the maximum of its distances to the ingroup taxa; a stable ascending sort;
+ *              candidates below 1.0 whose name is not an original ingroup taxon's are added until the target size is reached.
+ *   getMaxDistanceForEachOutgroupToIngroupSketch :738-783   every pool genome, with its maximum distance to the (final) ingroup.
+ *   getIngroupPairDistances :855-867 with StatisticsUtilities :158-173, :831-840, :938-949   mean (NaN entries skipped), standard
+ *              deviation with n - 1 (NaN for a single pair, -0.0 for none), maximum (NaN for none).
+ *   selectOutgroupCandidates :483-568   the threshold is max ingroup distance + sd * 0 (NaN when sd is NaN: then nothing is
+ *              acceptable); candidates in stable ascending order; one below 1.0 and above the threshold is acceptable, one below 1.0
+ *              and not above it is too near; the loop ends when `count` DISTINCT acceptable distances are met (so the last distance
+ *              contributes its first candidate only); up to `count` candidates by ascending distance are selected; when none is
+ *              acceptable, the first candidate of the largest too-near distance, one only.
+ *   run :112-195   the ingroup tree is built when !outgroup_only and expand_ingroup > 3, the second tree when neither flag is set
+ *              and expand_ingroup + the selected outgroups > 3: both conditions read the OPTION, not the ingroup's size, as the Java
+ *              does (with the default 0 no ingroup tree is written).  Where the Java would then hand NJ fewer than 4 taxa (it writes
+ *              "null") the tree is left out.  buildNJTreeOfTaxa :623-635 orders the taxa outgroups first.
+ * Not built: rooting (AdvancedTree.setOutGroup + getTreeString :637-640): the second tree is the UNROOTED NJ tree with the outgroup
+ * taxa first.  A genome is given with explicit lengths; its bytes may be anything. */
+typedef struct {
+    int nrecords;
+    const char *const *records;       /* [nrecords] bytes, not terminated */
+    const long long *lengths;         /* [nrecords] */
+} pml_genome;
+/* the window starts k_mash_hash stages at a time, and the sketch values k_mash_pairs takes at a time (tests aim at these boundaries) */
+int  pml_mash_tile(void);
+int  pml_mash_chunk(void);
+/* Genomes to sketches: values_out [ngenomes][s] (row g: len_out[g] ascending values, then zeros).  The caller may keep them between
+ * runs, the role of the reference's -outgroup_sketch file.  Genomes are hashed in sub-batches that fit the HBM budget (0.85 of free
+ * HBM, or PML_HBM_BUDGET_MB); a single genome that does not fit, or one of 2^31 bytes or more, is PML_ENOMEM.  k outside 1..32 and
+ * s < 1 are PML_EINVAL.  Selection: a histogram of the values' leading 12 bits gives every genome a cut, the values under it are
+ * compacted, sorted (rocPRIM's segmented radix sort) and deduplicated; a genome with fewer than s distinct values under a cut that
+ * is not yet everything gets a cut at least twice as wide and its sub-batch is repeated (pml_mash_stats counts these). */
+int  pml_mash_sketch(pml_ctx *ctx, int ngenomes, const pml_genome *genomes, int k, int s, unsigned long long *values_out, int *len_out);
+/* every pair of two sets of host sketches ([n][s] rows as pml_mash_sketch leaves them; each ascending and distinct, else PML_EINVAL):
+ * common_out, denom_out, distance_out are na x nb, row major; each may be NULL.  digits as above (0 = the double) */
+int  pml_mash_dist(pml_ctx *ctx, int na, const unsigned long long *a_values, const int *a_len, int nb, const unsigned long long *b_values, const int *b_len,
+                   int k, int s, int digits, int *common_out, int *denom_out, double *distance_out);
+/* the same from genomes: the sketches never leave HBM */
+int  pml_mash_distances(pml_ctx *ctx, int na, const pml_genome *a, int nb, const pml_genome *b, int k, int s, int digits, int *common_out, int *denom_out,
+                        double *distance_out);
+/* test door: what k_mash_hash wrote for one genome: one value per byte of every record in order (sum of lengths values), 2^64 - 1
+ * where no valid window starts */
+int  pml_debug_mash_hashes(pml_ctx *ctx, const pml_genome *genome, int k, unsigned long long *values_out);
+/* test door: on != 0 makes every cut take everything (the full-sort baseline of tools/measure_mash.py) */
+int  pml_debug_mash_full_sort(pml_ctx *ctx, int on);
+/* launches[5] = k_mash_hash, k_mash_cut, k_mash_compact, k_mash_unique, k_mash_pairs on this context so far; with cfg.profile = 1
+ * total_ms[4] = the uploads, k_mash_hash, the selection (cut, compaction, sort, deduplication), k_mash_pairs; *repeats = sub-batches
+ * repeated with a raised cut.  Never reset. */
+int  pml_mash_stats(pml_ctx *ctx, long long *launches, double *total_ms, long long *repeats);
+/* host-only, no context: the rule above over bytes (csrc/mash_host.cpp).  pml_mash_hashes_host = pml_debug_mash_hashes' values */
+int  pml_mash_murmur3(const void *key, long long len, unsigned seed, unsigned long long out[2]);
+int  pml_mash_hashes_host(const pml_genome *genome, int k, unsigned long long *values_out);
+int  pml_mash_sketch_host(const pml_genome *genome, int k, int s, unsigned long long *values_out /* [s] */, int *len_out);
+int  pml_mash_pair_host(const unsigned long long *a, int na, const unsigned long long *b, int nb, int s, int *common_out, int *denom_out);
+double pml_mash_distance_of(int common, int denom, int k, int digits);
+/* host-only: the Java's routines on indices.  d is [n_pool][n_in], the pool genomes' distances to the ingroup taxa */
+int  pml_mash_candidate_distances(int n_in, int n_pool, const double *d, double *cand_out /* [n_pool] */);
+int  pml_mash_expand_ingroup(int n_in, int n_pool, const double *d, const unsigned char *pool_is_ingroup /* [n_pool] or NULL */, int target,
+                             int *added_out /* [n_pool] pool indices in the order added */, int *nadded_out);
+int  pml_mash_pair_stats(int n, const double *d, double out3[3] /* mean, sd, max */);
+int  pml_mash_select_outgroup(int n, const double *cand, double max_ingroup, double sd, int count, int *selected_out /* [n] */, int *nselected_out);
+/* NeighborMasher.run() as one call.  PML_EINVAL with a message: k, s as above, an empty name list (the pool may be empty only with
+ * ingroup_only and no expansion), a taxon name twice in one list, and -- here only -- a genome whose sketch is empty.  A pool genome
+ * that carries an ingroup taxon's name is never added by the expansion. */
+typedef struct {
+    int n_ingroup, n_pool;
+    const pml_genome *ingroup, *pool;
+    const char *const *ingroup_names, *const *pool_names;
+    int k, s;                         /* the Java's defaults: 21, 100000 */
+    int outgroup_count;               /* 3 */
+    int expand_ingroup;               /* 0 */
+    int ingroup_only, outgroup_only;
+    int digits;                       /* 6 = as read from mash's text, 0 = the double */
+} pml_neighbor_masher_opts;
+typedef struct {
+    int n_ingroup; int *ingroup;      /* the final ingroup: i < opts->n_ingroup = ingroup genome i, else pool genome i - opts->n_ingroup */
+    int n_outgroup; int *outgroup;    /* pool indices, in the order selected */
+    int n_pool; double *candidate_distance;            /* [n_pool] maximum distance to the final ingroup; NULL with ingroup_only */
+    double mean, sd, max;             /* of the final ingroup's pair distances (NaN with ingroup_only) */
+    int n_taxa; int *taxa;            /* the outgroups, then the ingroup, indexed as `ingroup` is */
+    double *distance; int *common, *denom;             /* [n_taxa][n_taxa] as fed to NJ: symmetric from the upper triangle, 0 diagonal */
+    int *sketch_len;                  /* [opts->n_ingroup + opts->n_pool] */
+    char *ingroup_tree, *rooted_tree; /* NULL where run() builds none; the ingroup tree is NJ of the trailing block of `distance` */
+} pml_neighbor_masher_result;
+int  pml_neighbor_masher(pml_ctx *ctx, const pml_neighbor_masher_opts *opts, pml_neighbor_masher_result *result);
+void pml_neighbor_masher_result_free(pml_neighbor_masher_result *result);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);

@@ -39,7 +39,31 @@ SYMBOLS = [
     "pml_gene_steps_stats",
     "pml_bootstrap2", "pml_boot_draws_host", "pml_boot_tile", "pml_debug_boot_replicate", "pml_boot_stats",
     "pml_boot_replicate_lnls",
+    "pml_mash_tile", "pml_mash_chunk", "pml_mash_sketch", "pml_mash_dist", "pml_mash_distances", "pml_debug_mash_hashes", "pml_debug_mash_full_sort",
+    "pml_mash_stats", "pml_mash_murmur3", "pml_mash_hashes_host", "pml_mash_sketch_host", "pml_mash_pair_host", "pml_mash_distance_of",
+    "pml_mash_candidate_distances", "pml_mash_expand_ingroup", "pml_mash_pair_stats", "pml_mash_select_outgroup",
+    "pml_neighbor_masher", "pml_neighbor_masher_result_free",
 ]
+
+
+class Genome(C.Structure):
+    _fields_ = [("nrecords", C.c_int), ("records", C.POINTER(C.c_char_p)), ("lengths", C.POINTER(C.c_longlong))]
+
+
+class NeighborMasherOpts(C.Structure):
+    _fields_ = [("n_ingroup", C.c_int), ("n_pool", C.c_int), ("ingroup", C.POINTER(Genome)), ("pool", C.POINTER(Genome)),
+                ("ingroup_names", C.POINTER(C.c_char_p)), ("pool_names", C.POINTER(C.c_char_p)),
+                ("k", C.c_int), ("s", C.c_int), ("outgroup_count", C.c_int), ("expand_ingroup", C.c_int),
+                ("ingroup_only", C.c_int), ("outgroup_only", C.c_int), ("digits", C.c_int)]
+
+
+class NeighborMasherResult(C.Structure):
+    _fields_ = [("n_ingroup", C.c_int), ("ingroup", C.POINTER(C.c_int)), ("n_outgroup", C.c_int), ("outgroup", C.POINTER(C.c_int)),
+                ("n_pool", C.c_int), ("candidate_distance", C.POINTER(C.c_double)),
+                ("mean", C.c_double), ("sd", C.c_double), ("max", C.c_double),
+                ("n_taxa", C.c_int), ("taxa", C.POINTER(C.c_int)),
+                ("distance", C.POINTER(C.c_double)), ("common", C.POINTER(C.c_int)), ("denom", C.POINTER(C.c_int)),
+                ("sketch_len", C.POINTER(C.c_int)), ("ingroup_tree", C.c_void_p), ("rooted_tree", C.c_void_p)]
 
 
 class TreeCompareOpts(C.Structure):
@@ -334,5 +358,27 @@ def load():
     L.pml_debug_boot_replicate.argtypes = [vp, C.c_int, ap, C.c_int, ip, C.c_ulonglong, C.c_int, C.c_int, ip, ip, ip] + [C.POINTER(vp)] * 6
     L.pml_boot_stats.argtypes = [vp, lp, dp, dp]
     L.pml_boot_replicate_lnls.argtypes = [vp, C.c_int, dp]
+    gp, up, ulp = C.POINTER(Genome), C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)
+    L.pml_mash_tile.argtypes = []
+    L.pml_mash_chunk.argtypes = []
+    L.pml_mash_sketch.argtypes = [vp, C.c_int, gp, C.c_int, C.c_int, ulp, ip]
+    L.pml_mash_dist.argtypes = [vp, C.c_int, ulp, ip, C.c_int, ulp, ip, C.c_int, C.c_int, C.c_int, ip, ip, dp]
+    L.pml_mash_distances.argtypes = [vp, C.c_int, gp, C.c_int, gp, C.c_int, C.c_int, C.c_int, ip, ip, dp]
+    L.pml_debug_mash_hashes.argtypes = [vp, gp, C.c_int, ulp]
+    L.pml_debug_mash_full_sort.argtypes = [vp, C.c_int]
+    L.pml_mash_stats.argtypes = [vp, lp, dp, lp]
+    L.pml_mash_murmur3.argtypes = [C.c_char_p, C.c_longlong, C.c_uint, ulp]
+    L.pml_mash_hashes_host.argtypes = [gp, C.c_int, ulp]
+    L.pml_mash_sketch_host.argtypes = [gp, C.c_int, C.c_int, ulp, ip]
+    L.pml_mash_pair_host.argtypes = [ulp, C.c_int, ulp, C.c_int, C.c_int, ip, ip]
+    L.pml_mash_distance_of.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pml_mash_distance_of.restype = C.c_double
+    L.pml_mash_candidate_distances.argtypes = [C.c_int, C.c_int, dp, dp]
+    L.pml_mash_expand_ingroup.argtypes = [C.c_int, C.c_int, dp, up, C.c_int, ip, ip]
+    L.pml_mash_pair_stats.argtypes = [C.c_int, dp, dp]
+    L.pml_mash_select_outgroup.argtypes = [C.c_int, dp, C.c_double, C.c_double, C.c_int, ip, ip]
+    L.pml_neighbor_masher.argtypes = [vp, C.POINTER(NeighborMasherOpts), C.POINTER(NeighborMasherResult)]
+    L.pml_neighbor_masher_result_free.argtypes = [C.POINTER(NeighborMasherResult)]
+    L.pml_neighbor_masher_result_free.restype = None
     _lib = L
     return L

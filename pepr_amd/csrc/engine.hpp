@@ -52,7 +52,11 @@ struct Ctx {
     // pml_boot_stats: k_boot_count, k_boot_index, k_boot_gather, k_boot_pairs launches, (profile mode) their HIP-event times, and the
     // host wall time of the replicate builds (count .. NJ starts / tip rows)
     long long boot_launches[4] = {0, 0, 0, 0}; double boot_ms[4] = {0, 0, 0, 0}, boot_build_ms = 0;
-    std::vector<double> boot_last_lnl;                           // the ML replicates' lnL of the last pml_bootstrap2 call (pml_boot_replicate_lnls)
+    // pml_mash_stats: k_mash_hash, k_mash_cut, k_mash_compact, k_mash_unique, k_mash_pairs launches; (profile mode) HIP-event times of
+    // the uploads, k_mash_hash, the selection (cut .. unique) and k_mash_pairs; sub-batches whose cut was raised and repeated
+    long long mash_launches[5] = {0, 0, 0, 0, 0}, mash_repeats = 0; double mash_ms[4] = {0, 0, 0, 0};
+    bool mash_full_sort = false;                                 // pml_debug_mash_full_sort: every genome's cut takes everything
+    std::vector<double> boot_last_lnl;                          // the ML replicates' lnL of the last pml_bootstrap2 call (pml_boot_replicate_lnls)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;
     std::vector<hipEvent_t> pool;

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "gblocks.hpp"
+#include "mash.hpp"
 #include "treecmp.hpp"
 
 namespace pml {
@@ -388,5 +389,20 @@ void launch_reduce(const ReduceReq *reqs, int n, hipStream_t s, hipEvent_t start
 void launch_newton(const ModelDev *model, const NewtonReq *reqs, const int *tickets, int nreg, int nstream, NewtonCtl *ctl, hipStream_t s);
 // the no-exchange fallback: one workgroup per listed request (register-form requests first), same bits as the split form
 void launch_newton_seq(const ModelDev *model, const NewtonReq *reqs, const int *req_list, int nreg, int nstream, NewtonCtl *ctl, hipStream_t s);
+
+// The MinHash path (mash.hip; the rule is in include/peprml.h, the shared pieces in mash.hpp).  A batch of genomes is one byte
+// buffer, every record followed by MASH_SEP; values[] has one entry per byte.  A span is a run of whole tiles of one genome.
+struct MashSpan { unsigned begin, end; int genome; };
+void launch_mash_hash(const uint8_t *bytes, unsigned nbytes, const MashSpan *spans, int nspans, int k, uint64_t *values, unsigned long long *nvalid, unsigned *hist,
+                      hipStream_t s);
+void launch_mash_cut(const unsigned *hist, const unsigned long long *nvalid, const int *min_bins, int ngenomes, int s, int *cut_bins, unsigned *count, hipStream_t st);
+void launch_mash_compact(const uint64_t *values, const MashSpan *spans, int nspans, const unsigned *first, const int *cut_bins, int k, uint64_t *comp, unsigned *count,
+                         hipStream_t s);
+// tmp == nullptr: only tmp_bytes is set.  Sorts comp[first[g] .. first[g] + count[g]) of every genome into sorted[] at the same place
+hipError_t launch_mash_sort(void *tmp, size_t &tmp_bytes, const uint64_t *comp, uint64_t *sorted, unsigned total, int ngenomes, const unsigned *first,
+                            const unsigned *count, unsigned *seg_end, int k, hipStream_t s);
+void launch_mash_unique(const uint64_t *sorted, const unsigned *first, const unsigned *count, int ngenomes, int s, uint64_t *sketch, int *len, hipStream_t st);
+// out[r * ncols + c] = (common, denom) of the sketches rows[r] and cols[c]; nrows <= 65535
+void launch_mash_pairs(const uint64_t *sketch, const int *len, const int *rows, int nrows, const int *cols, int ncols, int s, int2 *out, hipStream_t st);
 
 }  // namespace pml

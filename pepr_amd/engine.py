@@ -779,6 +779,87 @@ class Context:
         self._check(self.L.pml_gblocks_stats(self.ptr, C.byref(a), C.byref(b), ms))
         return {"class_launches": a.value, "select_launches": b.value, "class_ms": ms[0], "select_ms": ms[1], "upload_ms": ms[2]}
 
+    # ---- NeighborMasher: MinHash sketches, Mash distances, selection and NJ (include/peprml.h; parity with mash is unpinned) ----
+    def mash_sketch(self, genomes, k=21, s=100000):
+        """Genomes (each a list of records, bytes or str) -> a list of uint64 arrays: every genome's sketch, the ascending
+        min(s, D) smallest distinct values.  They can be kept and handed to mash_dist later."""
+        keep = []
+        n = len(genomes)
+        out = np.zeros((n, s), dtype=np.uint64)
+        lens = (C.c_int * n)()
+        self._check(self.L.pml_mash_sketch(self.ptr, n, _genome_array(genomes, keep), int(k), int(s), _ulp(out), lens))
+        return [out[g, :lens[g]].copy() for g in range(n)]
+
+    def mash_dist(self, sketches_a, sketches_b, k=21, s=100000, digits=6):
+        """Every pair of two lists of sketches -> {"common", "denom" int32[na][nb], "distance" float64[na][nb]}.  digits: 6 = the
+        distance as NeighborMasher reads it from mash's text, None = the double."""
+        na, nb = len(sketches_a), len(sketches_b)
+        a, la = _sketch_rows(sketches_a, s)
+        b, lb = _sketch_rows(sketches_b, s)
+        common, denom, dist = np.zeros((na, nb), dtype=np.int32), np.zeros((na, nb), dtype=np.int32), np.zeros((na, nb))
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.pml_mash_dist(self.ptr, na, _ulp(a), la.ctypes.data_as(ip), nb, _ulp(b), lb.ctypes.data_as(ip), int(k), int(s), int(digits or 0),
+                                         common.ctypes.data_as(ip), denom.ctypes.data_as(ip), _dp(dist)))
+        return {"common": common, "denom": denom, "distance": dist}
+
+    def mash_distances(self, genomes_a, genomes_b, k=21, s=100000, digits=6):
+        """mash_dist of the genomes' sketches without the sketches leaving the device"""
+        keep = []
+        na, nb = len(genomes_a), len(genomes_b)
+        common, denom, dist = np.zeros((na, nb), dtype=np.int32), np.zeros((na, nb), dtype=np.int32), np.zeros((na, nb))
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.pml_mash_distances(self.ptr, na, _genome_array(genomes_a, keep), nb, _genome_array(genomes_b, keep), int(k), int(s), int(digits or 0),
+                                              common.ctypes.data_as(ip), denom.ctypes.data_as(ip), _dp(dist)))
+        return {"common": common, "denom": denom, "distance": dist}
+
+    def debug_mash_hashes(self, genome, k=21):
+        """Test door of k_mash_hash: one uint64 per byte of every record in order; MASH_INVALID where no valid window starts"""
+        keep = []
+        g = _genome_array([genome], keep)
+        out = np.zeros(max(sum(len(r) for r in genome), 1), dtype=np.uint64)
+        self._check(self.L.pml_debug_mash_hashes(self.ptr, g, int(k), _ulp(out)))
+        return out[:sum(len(r) for r in genome)]
+
+    def debug_mash_full_sort(self, on):
+        """Test / measurement door: every cut takes everything, i.e. all values of a genome are sorted (the baseline)"""
+        self._check(self.L.pml_debug_mash_full_sort(self.ptr, int(bool(on))))
+
+    def mash_stats(self):
+        """Launches of the five MinHash kernels on this context so far, (profile mode) summed HIP-event times in ms, and how many
+        sub-batches were repeated with a raised cut"""
+        n, ms, rep = (C.c_longlong * 5)(), (C.c_double * 4)(), C.c_longlong()
+        self._check(self.L.pml_mash_stats(self.ptr, n, ms, C.byref(rep)))
+        return {"hash_launches": n[0], "cut_launches": n[1], "compact_launches": n[2], "unique_launches": n[3], "pairs_launches": n[4],
+                "upload_ms": ms[0], "hash_ms": ms[1], "select_ms": ms[2], "pairs_ms": ms[3], "repeats": rep.value}
+
+    def neighbor_masher(self, ingroup, pool, k=21, s=100000, outgroup_count=3, expand_ingroup=0, ingroup_only=False, outgroup_only=False, digits=6):
+        """NeighborMasher.run() as one call.  ingroup, pool: lists of (taxon name, genome).  -> {"ingroup": the final ingroup's
+        names, "outgroup": the selected pool names, "ingroup_index" / "outgroup_index", "candidate_distance", "mean", "sd", "max",
+        "taxa" (outgroups first), "distance", "common", "denom" (len(taxa) squared, as fed to NJ), "sketch_len", "ingroup_tree",
+        "rooted_tree" (None where run() builds none; the second tree is NOT rooted: include/peprml.h)}"""
+        keep = []
+        ni, npool = len(ingroup), len(pool)
+        names = [t[0] for t in ingroup] + [t[0] for t in pool]
+        ina = (C.c_char_p * max(ni, 1))(*[t[0].encode() for t in ingroup])
+        pna = (C.c_char_p * max(npool, 1))(*[t[0].encode() for t in pool])
+        o = _lib.NeighborMasherOpts(ni, npool, _genome_array([t[1] for t in ingroup], keep), _genome_array([t[1] for t in pool], keep), ina, pna,
+                                    int(k), int(s), int(outgroup_count), int(expand_ingroup), int(bool(ingroup_only)), int(bool(outgroup_only)), int(digits or 0))
+        r = _lib.NeighborMasherResult()
+        self._check(self.L.pml_neighbor_masher(self.ptr, C.byref(o), C.byref(r)))
+        try:
+            T = r.n_taxa
+            ing, outg = [r.ingroup[i] for i in range(r.n_ingroup)], [r.outgroup[i] for i in range(r.n_outgroup)]
+            arr = lambda p, dt: np.array(p[:T * T], dtype=dt).reshape(T, T)      # noqa: E731
+            return {"ingroup": [names[i] for i in ing], "outgroup": [names[ni + p] for p in outg], "ingroup_index": ing, "outgroup_index": outg,
+                    "candidate_distance": np.array(r.candidate_distance[:r.n_pool]) if r.candidate_distance else None,
+                    "mean": r.mean, "sd": r.sd, "max": r.max, "taxa": [names[r.taxa[i]] for i in range(T)],
+                    "distance": arr(r.distance, np.float64), "common": arr(r.common, np.int32), "denom": arr(r.denom, np.int32),
+                    "sketch_len": [r.sketch_len[i] for i in range(ni + npool)],
+                    "ingroup_tree": C.string_at(r.ingroup_tree).decode() if r.ingroup_tree else None,
+                    "rooted_tree": C.string_at(r.rooted_tree).decode() if r.rooted_tree else None}
+        finally:
+            self.L.pml_neighbor_masher_result_free(C.byref(r))
+
     # ---- the gene homoplasy test of ConcatenatedSequenceAlignment (include/peprml.h pml_gene_steps, pml_step_thresholds) ----
     def gene_steps(self, genes, newick):
         """Per-column Fitch steps of the concatenation of `genes` on `newick`, the least steps each column can take, and the
@@ -1446,6 +1527,143 @@ def gblocks_flags_host(gene, params=None):
 def gblocks_chunk():
     """the columns k_gbselect scans at a time"""
     return _lib.load().pml_gblocks_chunk()
+
+
+MASH_INVALID = 0xFFFFFFFFFFFFFFFF     # what k_mash_hash writes where no valid window starts
+
+
+def _ulp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+
+def _genome_array(genomes, keep):
+    """genomes (each a list of records, bytes or str) as the pml_genome array the C ABI takes; a str is its latin-1 bytes"""
+    n = len(genomes)
+    arr = (_lib.Genome * max(n, 1))()
+    for g, recs in enumerate(genomes):
+        recs = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in recs]
+        ra = (C.c_char_p * max(len(recs), 1))(*recs)
+        la = (C.c_longlong * max(len(recs), 1))(*[len(r) for r in recs])
+        keep.extend([recs, ra, la])
+        arr[g] = _lib.Genome(len(recs), ra, la)
+    keep.append(arr)
+    return arr
+
+
+def _sketch_rows(sketches, s):
+    n = len(sketches)
+    rows, lens = np.zeros((max(n, 1), s), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32)
+    for g, sk in enumerate(sketches):
+        sk = np.asarray(sk, dtype=np.uint64)
+        if sk.size > s:
+            raise PmlError(EINVAL, "sketch %d has %d values, more than s = %d" % (g, sk.size, s))
+        rows[g, :sk.size] = sk
+        lens[g] = sk.size
+    return rows, lens
+
+
+def mash_tile():
+    """the window starts k_mash_hash stages at a time"""
+    return _lib.load().pml_mash_tile()
+
+
+def mash_chunk():
+    """the sketch values k_mash_pairs takes at a time"""
+    return _lib.load().pml_mash_chunk()
+
+
+def mash_murmur3(data, seed=0):
+    """Host only: MurmurHash3_x64_128 of bytes -> (h1, h2)"""
+    out = (C.c_ulonglong * 2)()
+    rc = _lib.load().pml_mash_murmur3(data, len(data), int(seed), out)
+    if rc:
+        raise PmlError(rc)
+    return out[0], out[1]
+
+
+def mash_hashes_host(genome, k=21):
+    """Host only: Context.debug_mash_hashes' values from the rule over bytes"""
+    keep = []
+    n = sum(len(r) for r in genome)
+    out = np.zeros(max(n, 1), dtype=np.uint64)
+    rc = _lib.load().pml_mash_hashes_host(_genome_array([genome], keep), int(k), _ulp(out))
+    if rc:
+        raise PmlError(rc, "k %r" % (k,))
+    return out[:n]
+
+
+def mash_sketch_host(genome, k=21, s=100000):
+    """Host only: one genome's sketch"""
+    keep = []
+    out, n = np.zeros(max(int(s), 1), dtype=np.uint64), C.c_int()
+    rc = _lib.load().pml_mash_sketch_host(_genome_array([genome], keep), int(k), int(s), _ulp(out), C.byref(n))
+    if rc:
+        raise PmlError(rc, "k %r, s %r" % (k, s))
+    return out[:n.value].copy()
+
+
+def mash_pair_host(a, b, s):
+    """Host only: (common, denom) of two sketches by the sequential loop that defines them"""
+    a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
+    c, d = C.c_int(), C.c_int()
+    rc = _lib.load().pml_mash_pair_host(_ulp(a), a.size, _ulp(b), b.size, int(s), C.byref(c), C.byref(d))
+    if rc:
+        raise PmlError(rc, "s %r" % (s,))
+    return c.value, d.value
+
+
+def mash_distance_of(common, denom, k, digits=None):
+    """Host only: the distance of a pair's two integers; digits = 6 as NeighborMasher reads it from mash's text"""
+    return _lib.load().pml_mash_distance_of(int(common), int(denom), int(k), int(digits or 0))
+
+
+def _pool_table(d):
+    d = np.ascontiguousarray(np.asarray(d, dtype=np.float64))
+    if d.ndim != 2 or d.shape[1] < 1:
+        raise PmlError(EINVAL, "the distance table must be pool x ingroup")
+    return d
+
+
+def mash_candidate_distances(d):
+    """Host only: getMaxDistanceForEachOutgroupToIngroupSketch on a pool x ingroup table"""
+    d = _pool_table(d)
+    out = np.zeros(max(d.shape[0], 1))
+    rc = _lib.load().pml_mash_candidate_distances(d.shape[1], d.shape[0], _dp(d), _dp(out))
+    if rc:
+        raise PmlError(rc)
+    return out[:d.shape[0]]
+
+
+def mash_expand_ingroup(d, target, pool_is_ingroup=None):
+    """Host only: expandIngroup on a pool x ingroup table -> the pool indices added, in order"""
+    d = _pool_table(d)
+    n = d.shape[0]
+    flags = None if pool_is_ingroup is None else (C.c_ubyte * max(n, 1))(*[int(bool(x)) for x in pool_is_ingroup])
+    added, na = (C.c_int * max(n, 1))(), C.c_int()
+    rc = _lib.load().pml_mash_expand_ingroup(d.shape[1], n, _dp(d), flags, int(target), added, C.byref(na))
+    if rc:
+        raise PmlError(rc)
+    return [added[i] for i in range(na.value)]
+
+
+def mash_pair_stats(distances):
+    """Host only: StatisticsUtilities' mean, standard deviation and maximum as getIngroupPairDistances' caller uses them"""
+    d = np.ascontiguousarray(np.asarray(distances, dtype=np.float64).reshape(-1))
+    out = (C.c_double * 3)()
+    rc = _lib.load().pml_mash_pair_stats(d.size, _dp(d) if d.size else None, out)
+    if rc:
+        raise PmlError(rc)
+    return out[0], out[1], out[2]
+
+
+def mash_select_outgroup(cand, max_ingroup, sd, count):
+    """Host only: selectOutgroupCandidates -> the selected candidates' indices, in order"""
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.float64).reshape(-1))
+    sel, ns = (C.c_int * max(c.size, 1))(), C.c_int()
+    rc = _lib.load().pml_mash_select_outgroup(c.size, _dp(c) if c.size else None, float(max_ingroup), float(sd), int(count), sel, C.byref(ns))
+    if rc:
+        raise PmlError(rc)
+    return [sel[i] for i in range(ns.value)]
 
 
 def _gene_steps_struct(result):

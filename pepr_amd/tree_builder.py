@@ -393,6 +393,79 @@ class MSATrimmer:
         return self._trim(alignment, engine.TRIM_TOPOLOGICAL, None)
 
 
+class NeighborMasher:
+    """util/NeighborMasher.java with the Java's setter names: run() (:112-195) picks the ingroup's expansion and the outgroups from
+    a pool and builds the two NJ trees, from MinHash sketches and Mash distances computed on the device (Context.neighbor_masher;
+    the rule is in include/peprml.h and its parity with the mash binary is unpinned).  Genomes are given as (taxon name, records)
+    instead of file names; tools/pepr_neighbor_masher.py reads the files.  The second tree is the unrooted NJ tree with the
+    outgroup taxa first: rooting (:637-640) is not built.  digits = 6 feeds the selection and NJ the distance as the Java reads it
+    from mash's text, None the double."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+        self.mashKmerLength, self.mashSketchSize = 21, 100000        # :45, :49
+        self.outgroupCount, self.expandedIngroupSize = 3, 0          # :53, :57
+        self.ingroupOnly = self.outgroupOnly = False
+        self.runName = None
+        self.ingroup, self.pool = [], []
+        self.digits = 6
+        self.result = None
+
+    def setMashKmerLength(self, k):
+        self.mashKmerLength = int(k)
+
+    def setMashSketchSize(self, s):
+        self.mashSketchSize = int(s)
+
+    def setOutgroupCount(self, n):
+        self.outgroupCount = int(n)
+
+    def setExpandedIngroupSize(self, n):
+        self.expandedIngroupSize = int(n)
+
+    def setIngroupTreeOnly(self, b):          # the Java's name for -ingroup_only (:873)
+        self.ingroupOnly = bool(b)
+
+    def setOutgroupOnly(self, b):
+        self.outgroupOnly = bool(b)
+
+    def setRunName(self, name):
+        self.runName = name
+
+    def getRunName(self):
+        return self.runName
+
+    def setIngroupGenomes(self, named_genomes):
+        """[(taxon name, records)] in place of setIngroupGenomeFileNames"""
+        self.ingroup = list(named_genomes)
+
+    def setOutgroupGenomes(self, named_genomes):
+        """[(taxon name, records)] in place of setOutgroupGenomeFileNames: the pool of candidates"""
+        self.pool = list(named_genomes)
+
+    def setDistanceDigits(self, digits):
+        self.digits = digits
+
+    def run(self):
+        ctx = self.ctx or default_context()
+        self.result = ctx.neighbor_masher(self.ingroup, self.pool, k=self.mashKmerLength, s=self.mashSketchSize, outgroup_count=self.outgroupCount,
+                                          expand_ingroup=self.expandedIngroupSize, ingroup_only=self.ingroupOnly, outgroup_only=self.outgroupOnly,
+                                          digits=self.digits)
+        return self.result
+
+    def getIngroupTaxa(self):
+        return list(self.result["ingroup"])
+
+    def getSelectedOutgroupTaxa(self):
+        return list(self.result["outgroup"])
+
+    def getIngroupTree(self):
+        return self.result["ingroup_tree"]
+
+    def getRootedTree(self):
+        return self.result["rooted_tree"]
+
+
 class ConcatenatedSequenceAlignment:
     """.../pepr/alignment/ConcatenatedSequenceAlignment.java's gene homoplasy test (:65-425) on the device (Context.gene_steps,
     Context.step_thresholds; the rules are in include/peprml.h).  In the reference nothing ever calls setStepsPerSite
