@@ -1074,6 +1074,91 @@ typedef struct {
 int  pml_neighbor_masher(pml_ctx *ctx, const pml_neighbor_masher_opts *opts, pml_neighbor_masher_result *result);
 void pml_neighbor_masher_result_free(pml_neighbor_masher_result *result);
 
+/* ---- Homolog groups: Markov clustering of the hit graph (PhyloPipeline.java:357-406) ----
+ * What the reference does between its all-vs-all search and its trees: filterHitPairFile :989-1024 or filterForBidirectional
+ * :911-987, `mcl <hits> --abc -I 1.5` (runMCL :882-909), one set_<k>.faa per line of mcl's output (SequenceSetExtractor) and
+ * the choice of the sets that become genes (SequenceSetProviderImpl, PhylogenomicPipeline2.createInputSequenceSetProvider
+ * :564-605).  PINNED: clusters, their order and their members' order equal mcl 09-308's on the committed cases
+ * (tests/golden/mcl_cases.json, written by tests/golden/make_mcl_cases.py beside the binary); the filters and the selection are
+ * restated from the Java source.  The rule:
+ *   nodes      the labels of the table in order of first appearance, id1 before id2 on a line
+ *   arcs       `a b w`, a != b, sets G[a][b] and G[b][a] to the larger of their present value and w (a mirror with a max
+ *              combine).  A self hit only makes its label a node.  A weight that is not finite or is <= 0 is PML_EINVAL
+ *   loops      G[j][j] = the largest entry of column j, 1 where the column is otherwise empty; M = G, every column over its sum
+ *   iteration  at most max_iter (10000) times: M <- M M; entries below 1 / prune_inverse (10000) become 0 and the columns are
+ *              renormalised; chaos = max_j (max_i M_ij - sum_i M_ij^2); M_ij <- M_ij^inflation and the columns are renormalised;
+ *              stop when chaos < chaos_eps (1e-3)
+ *   reading    attractors are the i with M_ii > 0; attractors a, b with M_ab > 0 are one system; node j joins the system of the
+ *              attractor row with the largest M_aj, the lowest index of equals (a node of a matrix without attractors stays alone)
+ *   order      clusters by size, largest first, ties to the lower smallest member; members ascending by index.  mcl's text is
+ *              one cluster per line, labels joined by tabs; set_<k>.faa is line k (from 0), so the order is part of the contract
+ *   components connected components of G are clustered independently (the matrix is block diagonal); the iteration count
+ *              reported is the slowest component's
+ * NOT BUILT: mcl's selection and recovery pruning (-S 1100 -R 1400 -pct 90), which act only on columns of more than 1100 entries
+ * -- parity is claimed for components up to that size only; mcl's other input modes; sparse expansion (every component is a dense
+ * f64 matrix: one of n nodes takes 16 n^2 bytes rounded up to tiles, and one that does not fit the HBM budget -- 0.85 of free HBM,
+ * or PML_HBM_BUDGET_MB -- is PML_ENOMEM with its size in the message).
+ * Device classes (pml_mcl_class_limits): components of up to limits[0] nodes run packed, four to a workgroup, one wavefront each;
+ * up to limits[1] one workgroup each, both with the matrix in LDS and the whole iteration inside ONE launch; larger ones in HBM,
+ * a tiled expansion (tile limits[2]) and a column kernel per iteration, the host reading one flag per component between them.
+ * All arithmetic is f64, the expansion on v_mfma_f64_16x16x4_f64. */
+typedef struct pml_mcl_opts {
+    double inflation, prune_inverse, chaos_eps;       /* 0 = 1.5, 10000, 1e-3 */
+    int max_iter, pad;                                /* 0 = 10000 */
+} pml_mcl_opts;
+/* the integer-level call: nodes 0 .. n-1, arcs (a[i], b[i], w[i]).  cluster_of_out[n] numbers the clusters in output order */
+int  pml_mcl_cluster(pml_ctx *ctx, int n, long long narcs, const int *a, const int *b, const double *w, const pml_mcl_opts *opts,
+                     int *cluster_of_out, int *nclusters_out, int *iters_out);
+/* the same rule in plain C++ loops, no context (csrc/mcl_host.cpp): the CPU tests' subject and the timing baseline */
+int  pml_mcl_cluster_host(int n, long long narcs, const int *a, const int *b, const double *w, const pml_mcl_opts *opts,
+                          int *cluster_of_out, int *nclusters_out, int *iters_out);
+/* The hit table to gene sets.  score_field 11: the table is BLAST's tabular output and goes through filterHitPairFile, or with
+ * `bidirectional` through filterForBidirectional(file, 11); score_field 2: it already is `id1 id2 score` and is clustered as
+ * it stands (bidirectional must be 0).  Selection runs when taxon_labels is given: label taxon_labels[i] belongs to taxon
+ * taxon_of[i] (a clustered label without an entry is PML_EINVAL): clusters with min_taxa <= members <= max_taxa (a sequence
+ * count); with rep_only those in which no taxon occurs twice; then, if more than target_min_gene remain, for t = min_taxa + 1 ..
+ * target_ntax: when at least target_min_gene clusters have >= t distinct taxa, those with fewer are dropped. */
+typedef struct {
+    const char *table; long long table_bytes;
+    int score_field, bidirectional;
+    pml_mcl_opts mcl;
+    int ntaxon_labels; const char *const *taxon_labels; const int *taxon_of;
+    int min_taxa, max_taxa, rep_only, target_ntax, target_min_gene;
+} pml_homolog_groups_opts;
+typedef struct {
+    int nlabels; char **labels;                       /* the nodes */
+    int nclusters; long long *cluster_off;            /* [nclusters + 1] into members */
+    int *members;                                     /* [nlabels] node indices, cluster by cluster in output order */
+    char *mcl_text;                                   /* mcl's output file */
+    int nkept; int *kept;                             /* cluster indices the selection keeps, ascending (all without taxon_labels) */
+    int ncomponents, iterations;
+    char *filtered_text;                              /* the <hits>_filtered or <hits>_bidir file; NULL with score_field 2 */
+} pml_homolog_groups_result;
+int  pml_homolog_groups(pml_ctx *ctx, const pml_homolog_groups_opts *opts, pml_homolog_groups_result *result);
+void pml_homolog_groups_result_free(pml_homolog_groups_result *result);
+/* host-only, no context.  The filters return malloc'ed text (pml_free).  filterHitPairFile: fields 0, 1 and 11 of the lines
+ * with more than one field (a line with 2 .. 11 fields, the Java's exception, is PML_EINVAL).  filterForBidirectional: only
+ * lines with more than score_field fields count; pairs are unordered, self pairs included; the first sighting of a pair stores
+ * new Float(field), the next writes `id1 id2 <field text>` and `id2 id1 <Float.toString(stored)>` and forgets the pair, so a
+ * third sighting stores again.  Float.toString is restated for finite values: the shortest decimal that round-trips the f32,
+ * at least one digit behind the point, the E form outside [1e-3, 1e7); the known JDK cases that are not shortest are NOT
+ * reproduced. */
+int  pml_hits_filter_host(const char *table, long long table_bytes, char **text_out);
+int  pml_hits_bidirectional_host(const char *table, long long table_bytes, int score_field, char **text_out);
+int  pml_homolog_select_host(int nclusters, const long long *cluster_off, const int *members, const int *taxon_of_node, int min_taxa, int max_taxa,
+                             int rep_only, int target_ntax, int target_min_gene, int *kept_out /* [nclusters] */, int *nkept_out);
+/* test doors.  limits_out[4] = the packed class's and the LDS class's largest component, the expansion tile, 0 */
+int  pml_mcl_class_limits(int *limits_out);
+/* nsteps iterations (no convergence test) of ONE dense component in class force_class (0 packed, 1 LDS, 2 HBM; PML_EINVAL when n
+ * exceeds the class): matrix_in / matrix_out are n x n, row major ([i * n + j] = M_ij), matrix_in column stochastic;
+ * *chaos_out = the last iteration's chaos */
+int  pml_debug_mcl_steps(pml_ctx *ctx, int n, const double *matrix_in, const pml_mcl_opts *opts, int nsteps, int force_class, double *matrix_out,
+                         double *chaos_out);
+/* launches[8] = k_mcl_fill, k_mcl_packed, k_mcl_lds, k_mcl_expand, k_mcl_inflate, k_mcl_flag, k_mcl_read, sub-batches on this
+ * context so far; with cfg.profile = 1 total_ms[4] = uploads and fill, the packed class, the LDS class, the HBM class (its host
+ * loop included, by HIP events).  Never reset. */
+int  pml_mcl_stats(pml_ctx *ctx, long long *launches, double *total_ms);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);

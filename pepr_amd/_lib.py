@@ -43,7 +43,25 @@ SYMBOLS = [
     "pml_mash_stats", "pml_mash_murmur3", "pml_mash_hashes_host", "pml_mash_sketch_host", "pml_mash_pair_host", "pml_mash_distance_of",
     "pml_mash_candidate_distances", "pml_mash_expand_ingroup", "pml_mash_pair_stats", "pml_mash_select_outgroup",
     "pml_neighbor_masher", "pml_neighbor_masher_result_free",
+    "pml_mcl_cluster", "pml_mcl_cluster_host", "pml_homolog_groups", "pml_homolog_groups_result_free", "pml_hits_filter_host",
+    "pml_hits_bidirectional_host", "pml_homolog_select_host", "pml_mcl_class_limits", "pml_debug_mcl_steps", "pml_mcl_stats",
 ]
+
+
+class MclOpts(C.Structure):
+    _fields_ = [("inflation", C.c_double), ("prune_inverse", C.c_double), ("chaos_eps", C.c_double), ("max_iter", C.c_int), ("pad", C.c_int)]
+
+
+class HomologGroupsOpts(C.Structure):
+    _fields_ = [("table", C.c_char_p), ("table_bytes", C.c_longlong), ("score_field", C.c_int), ("bidirectional", C.c_int), ("mcl", MclOpts),
+                ("ntaxon_labels", C.c_int), ("taxon_labels", C.POINTER(C.c_char_p)), ("taxon_of", C.POINTER(C.c_int)),
+                ("min_taxa", C.c_int), ("max_taxa", C.c_int), ("rep_only", C.c_int), ("target_ntax", C.c_int), ("target_min_gene", C.c_int)]
+
+
+class HomologGroupsResult(C.Structure):
+    _fields_ = [("nlabels", C.c_int), ("labels", C.POINTER(C.c_char_p)), ("nclusters", C.c_int), ("cluster_off", C.POINTER(C.c_longlong)),
+                ("members", C.POINTER(C.c_int)), ("mcl_text", C.c_void_p), ("nkept", C.c_int), ("kept", C.POINTER(C.c_int)),
+                ("ncomponents", C.c_int), ("iterations", C.c_int), ("filtered_text", C.c_void_p)]
 
 
 class Genome(C.Structure):
@@ -380,5 +398,17 @@ def load():
     L.pml_neighbor_masher.argtypes = [vp, C.POINTER(NeighborMasherOpts), C.POINTER(NeighborMasherResult)]
     L.pml_neighbor_masher_result_free.argtypes = [C.POINTER(NeighborMasherResult)]
     L.pml_neighbor_masher_result_free.restype = None
+    mop = C.POINTER(MclOpts)
+    L.pml_mcl_cluster.argtypes = [vp, C.c_int, C.c_longlong, ip, ip, dp, mop, ip, ip, ip]
+    L.pml_mcl_cluster_host.argtypes = [C.c_int, C.c_longlong, ip, ip, dp, mop, ip, ip, ip]
+    L.pml_homolog_groups.argtypes = [vp, C.POINTER(HomologGroupsOpts), C.POINTER(HomologGroupsResult)]
+    L.pml_homolog_groups_result_free.argtypes = [C.POINTER(HomologGroupsResult)]
+    L.pml_homolog_groups_result_free.restype = None
+    L.pml_hits_filter_host.argtypes = [C.c_char_p, C.c_longlong, C.POINTER(vp)]
+    L.pml_hits_bidirectional_host.argtypes = [C.c_char_p, C.c_longlong, C.c_int, C.POINTER(vp)]
+    L.pml_homolog_select_host.argtypes = [C.c_int, lp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
+    L.pml_mcl_class_limits.argtypes = [ip]
+    L.pml_debug_mcl_steps.argtypes = [vp, C.c_int, dp, mop, C.c_int, C.c_int, dp, dp]
+    L.pml_mcl_stats.argtypes = [vp, lp, dp]
     _lib = L
     return L

@@ -56,6 +56,9 @@ struct Ctx {
     // the uploads, k_mash_hash, the selection (cut .. unique) and k_mash_pairs; sub-batches whose cut was raised and repeated
     long long mash_launches[5] = {0, 0, 0, 0, 0}, mash_repeats = 0; double mash_ms[4] = {0, 0, 0, 0};
     bool mash_full_sort = false;                                 // pml_debug_mash_full_sort: every genome's cut takes everything
+    // pml_mcl_stats: k_mcl_fill, k_mcl_lds<packed>, k_mcl_lds, k_mcl_expand, k_mcl_inflate, k_mcl_flag, k_mcl_read launches and sub-batches;
+    // (profile mode) HIP-event times of uploads and fill, the packed class, the LDS class, the HBM class
+    long long mcl_launches[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double mcl_ms[4] = {0, 0, 0, 0};
     std::vector<double> boot_last_lnl;                          // the ML replicates' lnL of the last pml_bootstrap2 call (pml_boot_replicate_lnls)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;

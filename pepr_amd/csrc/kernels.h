@@ -5,6 +5,7 @@
 
 #include "gblocks.hpp"
 #include "mash.hpp"
+#include "mcl.hpp"
 #include "treecmp.hpp"
 
 namespace pml {
@@ -404,5 +405,25 @@ hipError_t launch_mash_sort(void *tmp, size_t &tmp_bytes, const uint64_t *comp, 
 void launch_mash_unique(const uint64_t *sorted, const unsigned *first, const unsigned *count, int ngenomes, int s, uint64_t *sketch, int *len, hipStream_t st);
 // out[r * ncols + c] = (common, denom) of the sketches rows[r] and cols[c]; nrows <= 65535
 void launch_mash_pairs(const uint64_t *sketch, const int *len, const int *rows, int nrows, const int *cols, int ncols, int s, int2 *out, hipStream_t st);
+
+// Markov clustering (mcl.hip; the rule is in include/peprml.h, the shared pieces in mcl.hpp).  A sub-batch's components: mat =
+// the offset in doubles of its matrix in the pool (column major, column stride npad; LDS classes: npad = n, one matrix; HBM class:
+// npad = n rounded up to MCL_TILE, two matrices, the second behind the first), col0 = its first column in the call's per-column
+// arrays (the CSR's ptr, best, chaos_col), mask_off = its first word in the call's masks (n x mcl_words(n) words)
+struct MclComp { long long mat; int n, npad, col0, pad; long long mask_off; };
+struct MclRun { double inflation, prune_inverse, chaos_eps; int max_iter, pad; };
+size_t mcl_lds_bytes(bool packed);
+void launch_mcl_fill(const MclComp *comps, int ncomps, int max_n, const long long *ptr, const int *row, const double *val, double *pool, hipStream_t s);
+// the whole iteration and the reading of ncomps components of a class in one launch; n <= MCL_PACKED_MAX (packed) or MCL_LDS_MAX.
+// iters / chaos: per component of the sub-batch.  write_back: the final matrices replace the start matrices in the pool
+hipError_t launch_mcl_lds(bool packed, const MclComp *comps, int ncomps, double *pool, const MclRun &run, int *best, unsigned *mask, int *iters, double *chaos,
+                          bool write_back, hipStream_t s);
+// one iteration of the HBM class over the components active[0 .. nactive): parity 0 reads the first matrix and writes the second
+void launch_mcl_expand(const MclComp *comps, const int *active, int nactive, int max_npad, double *pool, int parity, hipStream_t s);
+void launch_mcl_inflate(const MclComp *comps, const int *active, int nactive, int max_n, double *pool, int parity, const MclRun &run, double *chaos_col, hipStream_t s);
+// iters[component] = it, chaos[component], flag[position in active] = chaos < chaos_eps
+void launch_mcl_flag(const MclComp *comps, const int *active, int nactive, const double *chaos_col, const MclRun &run, int it, int *iters, double *chaos, int *flag,
+                     hipStream_t s);
+void launch_mcl_read(const MclComp *comps, int ncomps, int max_n, const double *pool, const int *iters, int *best, unsigned *mask, hipStream_t s);
 
 }  // namespace pml

@@ -860,6 +860,63 @@ class Context:
         finally:
             self.L.pml_neighbor_masher_result_free(C.byref(r))
 
+    # ---- homolog groups: Markov clustering of the hit graph (include/peprml.h "Homolog groups") ----
+    def mcl_cluster(self, n, arcs, inflation=0.0, prune_inverse=0.0, chaos_eps=0.0, max_iter=0):
+        """Nodes 0 .. n-1 and arcs [(a, b, w)] -> {"clusters": lists of ascending node indices in mcl's output order, "cluster_of"
+        int32[n], "iterations": the slowest component's}.  Zeros are the defaults (1.5, 10000, 1e-3, 10000)."""
+        a, b, w = _arc_arrays(arcs)
+        out, nc, it = np.zeros(max(n, 1), dtype=np.int32), C.c_int(), C.c_int()
+        o = _lib.MclOpts(float(inflation), float(prune_inverse), float(chaos_eps), int(max_iter), 0)
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.pml_mcl_cluster(self.ptr, int(n), a.size, a.ctypes.data_as(ip), b.ctypes.data_as(ip), _dp(w), C.byref(o), out.ctypes.data_as(ip),
+                                           C.byref(nc), C.byref(it)))
+        return {"clusters": _clusters_of(out[:n], nc.value), "cluster_of": out[:n].copy(), "iterations": it.value}
+
+    def homolog_groups(self, table, score_field=11, bidirectional=False, inflation=0.0, prune_inverse=0.0, chaos_eps=0.0, max_iter=0, taxon_of=None,
+                       min_taxa=0, max_taxa=2 ** 31 - 1, rep_only=False, target_ntax=0, target_min_gene=0):
+        """The hit table (bytes or str) to PEPR's gene sets.  taxon_of: {label: taxon number} switches the set selection on.
+        -> {"labels", "clusters" (lists of node indices, mcl's order), "lines" (mcl's output lines), "mcl_text", "kept" (cluster
+        indices), "components", "iterations", "filtered_text" (the <hits>_filtered / <hits>_bidir file; None with score_field 2)}"""
+        t = table.encode() if isinstance(table, str) else bytes(table)
+        o = _lib.HomologGroupsOpts()
+        o.table, o.table_bytes, o.score_field, o.bidirectional = t, len(t), int(score_field), int(bool(bidirectional))
+        o.mcl = _lib.MclOpts(float(inflation), float(prune_inverse), float(chaos_eps), int(max_iter), 0)
+        if taxon_of:
+            labs = list(taxon_of)
+            la = (C.c_char_p * len(labs))(*[x.encode() for x in labs])
+            ta = (C.c_int * len(labs))(*[int(taxon_of[x]) for x in labs])
+            o.ntaxon_labels, o.taxon_labels, o.taxon_of = len(labs), la, ta
+        o.min_taxa, o.max_taxa, o.rep_only, o.target_ntax, o.target_min_gene = int(min_taxa), int(max_taxa), int(bool(rep_only)), int(target_ntax), int(target_min_gene)
+        r = _lib.HomologGroupsResult()
+        self._check(self.L.pml_homolog_groups(self.ptr, C.byref(o), C.byref(r)))
+        try:
+            labels = [r.labels[i].decode() for i in range(r.nlabels)]
+            off = [r.cluster_off[k] for k in range(r.nclusters + 1)]
+            clusters = [[r.members[i] for i in range(off[k], off[k + 1])] for k in range(r.nclusters)]
+            text = C.string_at(r.mcl_text).decode()
+            return {"labels": labels, "clusters": clusters, "lines": [ln for ln in text.split("\n") if ln], "mcl_text": text,
+                    "kept": [r.kept[i] for i in range(r.nkept)], "components": r.ncomponents, "iterations": r.iterations,
+                    "filtered_text": C.string_at(r.filtered_text).decode() if r.filtered_text else None}
+        finally:
+            self.L.pml_homolog_groups_result_free(C.byref(r))
+
+    def debug_mcl_steps(self, matrix, nsteps=1, force_class=0, inflation=0.0, prune_inverse=0.0):
+        """Test door: nsteps iterations of one column-stochastic matrix (M[i][j]) in class 0 (packed), 1 (LDS) or 2 (HBM) ->
+        (the matrix, the last iteration's chaos)"""
+        m = np.ascontiguousarray(matrix, dtype=np.float64)
+        out, chaos = np.zeros_like(m), C.c_double()
+        o = _lib.MclOpts(float(inflation), float(prune_inverse), 0.0, 0, 0)
+        self._check(self.L.pml_debug_mcl_steps(self.ptr, m.shape[0], _dp(m), C.byref(o), int(nsteps), int(force_class), _dp(out), C.byref(chaos)))
+        return out, chaos.value
+
+    def mcl_stats(self):
+        """Launches of the Markov clustering kernels on this context so far, sub-batches, and (profile mode) ms per stage"""
+        n, ms = (C.c_longlong * 8)(), (C.c_double * 4)()
+        self._check(self.L.pml_mcl_stats(self.ptr, n, ms))
+        return {"fill_launches": n[0], "packed_launches": n[1], "lds_launches": n[2], "expand_launches": n[3], "inflate_launches": n[4],
+                "flag_launches": n[5], "read_launches": n[6], "sub_batches": n[7],
+                "upload_fill_ms": ms[0], "packed_ms": ms[1], "lds_ms": ms[2], "hbm_ms": ms[3]}
+
     # ---- the gene homoplasy test of ConcatenatedSequenceAlignment (include/peprml.h pml_gene_steps, pml_step_thresholds) ----
     def gene_steps(self, genes, newick):
         """Per-column Fitch steps of the concatenation of `genes` on `newick`, the least steps each column can take, and the
@@ -1600,6 +1657,79 @@ def mash_sketch_host(genome, k=21, s=100000):
     if rc:
         raise PmlError(rc, "k %r, s %r" % (k, s))
     return out[:n.value].copy()
+
+
+def _arc_arrays(arcs):
+    arcs = list(arcs)
+    a = np.ascontiguousarray([t[0] for t in arcs], dtype=np.int32)
+    b = np.ascontiguousarray([t[1] for t in arcs], dtype=np.int32)
+    w = np.ascontiguousarray([t[2] for t in arcs], dtype=np.float64)
+    return a, b, w
+
+
+def _clusters_of(cluster_of, nclusters):
+    out = [[] for _ in range(nclusters)]
+    for i, k in enumerate(cluster_of):
+        out[int(k)].append(i)
+    return out
+
+
+def mcl_cluster_host(n, arcs, inflation=0.0, prune_inverse=0.0, chaos_eps=0.0, max_iter=0):
+    """Host only: Context.mcl_cluster's rule in plain C++ loops (the CPU tests' subject and the timing baseline)"""
+    a, b, w = _arc_arrays(arcs)
+    out, nc, it = np.zeros(max(n, 1), dtype=np.int32), C.c_int(), C.c_int()
+    o = _lib.MclOpts(float(inflation), float(prune_inverse), float(chaos_eps), int(max_iter), 0)
+    ip = C.POINTER(C.c_int)
+    rc = _lib.load().pml_mcl_cluster_host(int(n), a.size, a.ctypes.data_as(ip), b.ctypes.data_as(ip), _dp(w), C.byref(o), out.ctypes.data_as(ip), C.byref(nc), C.byref(it))
+    if rc:
+        raise PmlError(rc, "mcl_cluster_host")
+    return {"clusters": _clusters_of(out[:n], nc.value), "cluster_of": out[:n].copy(), "iterations": it.value}
+
+
+def _host_text(fn, *args):
+    p = C.c_void_p()
+    rc = fn(*args, C.byref(p))
+    if rc:
+        raise PmlError(rc, "the hit table")
+    try:
+        return C.string_at(p).decode()
+    finally:
+        _lib.load().pml_free(p)
+
+
+def hits_filter_host(table):
+    """Host only: filterHitPairFile (PhyloPipeline.java:989-1024) on a table's text"""
+    t = table.encode() if isinstance(table, str) else bytes(table)
+    return _host_text(_lib.load().pml_hits_filter_host, t, len(t))
+
+
+def hits_bidirectional_host(table, score_field=11):
+    """Host only: filterForBidirectional (PhyloPipeline.java:911-987) on a table's text"""
+    t = table.encode() if isinstance(table, str) else bytes(table)
+    return _host_text(_lib.load().pml_hits_bidirectional_host, t, len(t), int(score_field))
+
+
+def homolog_select_host(clusters, taxon_of_node, min_taxa, max_taxa, rep_only, target_ntax, target_min_gene):
+    """Host only: the set selection of createInputSequenceSetProvider on clusters of node indices -> kept cluster indices"""
+    off = np.zeros(len(clusters) + 1, dtype=np.int64)
+    for k, c in enumerate(clusters):
+        off[k + 1] = off[k] + len(c)
+    members = np.ascontiguousarray([i for c in clusters for i in c] or [0], dtype=np.int32)
+    tax = np.ascontiguousarray(list(taxon_of_node) or [0], dtype=np.int32)
+    kept, nk = np.zeros(max(len(clusters), 1), dtype=np.int32), C.c_int()
+    ip = C.POINTER(C.c_int)
+    rc = _lib.load().pml_homolog_select_host(len(clusters), off.ctypes.data_as(C.POINTER(C.c_longlong)), members.ctypes.data_as(ip), tax.ctypes.data_as(ip),
+                                             int(min_taxa), int(max_taxa), int(bool(rep_only)), int(target_ntax), int(target_min_gene), kept.ctypes.data_as(ip), C.byref(nk))
+    if rc:
+        raise PmlError(rc, "homolog_select_host")
+    return [int(k) for k in kept[:nk.value]]
+
+
+def mcl_class_limits():
+    """(the packed class's largest component, the LDS class's, the expansion tile)"""
+    out = (C.c_int * 4)()
+    _lib.load().pml_mcl_class_limits(out)
+    return out[0], out[1], out[2]
 
 
 def mash_pair_host(a, b, s):

@@ -466,6 +466,78 @@ class NeighborMasher:
         return self.result["rooted_tree"]
 
 
+def readFastaRecords(path):
+    """[(id token, [the record's lines])] of a FASTA file; the id token is FastaSequenceFile.getIDToken's (:192-204): the title up
+    to its first blank, without the '>'"""
+    out = []
+    with open(path) as fh:
+        for line in fh.read().split("\n"):
+            if line.startswith(">"):
+                sp = line.find(" ", 1)
+                out.append((line[1:sp if sp >= 0 else len(line)], [line]))
+            elif line and out:
+                out[-1][1].append(line)
+    return out
+
+
+class HomologGroups:
+    """PhyloPipeline.java:357-406 between the all-vs-all search and the trees: filterHitPairFile or filterForBidirectional,
+    `mcl --abc -I inflation` (runMCL :882-909) and SequenceSetExtractor's set files, with the clustering on the device
+    (Context.homolog_groups; the rule and what is pinned are in include/peprml.h).  run() writes <hits>_filtered or <hits>_bidir,
+    <...>_mclOut and hg_<run>/set_<k>.faa for every line k of mcl's output, members in the line's order.  A sequence's taxon is
+    the text of the last [...] of its title, or its file where the title has none; min_taxa .. target_min_gene are
+    createInputSequenceSetProvider's parameters (PhylogenomicPipeline2.java:564-605) and decide getSelectedSetFiles()."""
+
+    def __init__(self, hit_file, genome_files=(), ctx=None, run_name="run", out_dir=None, bidirectional=False, inflation=1.5, min_taxa=0,
+                 max_taxa=2 ** 31 - 1, rep_only=False, target_ntax=0, target_min_gene=0):
+        self.ctx, self.hit_file, self.genome_files = ctx, hit_file, list(genome_files)
+        self.run_name, self.out_dir = run_name, out_dir if out_dir is not None else os.path.dirname(os.path.abspath(hit_file))
+        self.bidirectional, self.inflation = bool(bidirectional), float(inflation)
+        self.min_taxa, self.max_taxa, self.rep_only, self.target_ntax, self.target_min_gene = min_taxa, max_taxa, rep_only, target_ntax, target_min_gene
+        self.result = None
+        self.set_files = []
+
+    def run(self):
+        ctx = self.ctx or default_context()
+        with open(self.hit_file, "rb") as fh:
+            table = fh.read()
+        records, taxon_names, taxon_of = {}, {}, {}
+        for fi, path in enumerate(self.genome_files):
+            for token, lines in readFastaRecords(path):
+                records[token] = lines                                # SequenceSetExtractor.buildSequenceIndexMap :379-392: the last file wins
+                title = lines[0]
+                lb, rb = title.rfind("["), title.rfind("]")
+                name = title[lb + 1:rb] if 0 <= lb < rb else "file %d" % fi
+                taxon_of[token] = taxon_names.setdefault(name, len(taxon_names))
+        r = ctx.homolog_groups(table, score_field=11, bidirectional=self.bidirectional, inflation=self.inflation, taxon_of=taxon_of or None,
+                               min_taxa=self.min_taxa, max_taxa=self.max_taxa, rep_only=self.rep_only, target_ntax=self.target_ntax,
+                               target_min_gene=self.target_min_gene)
+        self.result = r
+        filtered = self.hit_file + ("_bidir" if self.bidirectional else "_filtered")          # :919-920, :1002-1003
+        with open(filtered, "w") as fh:
+            fh.write(r["filtered_text"])
+        self.mcl_file = filtered + "_mclOut"                                                    # :889
+        with open(self.mcl_file, "w") as fh:
+            fh.write(r["mcl_text"])
+        hg = os.path.join(self.out_dir, "hg_" + self.run_name)                                  # :400-402
+        os.makedirs(hg, exist_ok=True)
+        self.set_files = []
+        for k, cluster in enumerate(r["clusters"]):                                             # SequenceSetExtractor.processSequenceSets :158-198
+            path = os.path.join(hg, "set_%d.faa" % k)
+            with open(path, "w") as fh:
+                for i in cluster:
+                    for line in records.get(r["labels"][i], ()):
+                        fh.write(line + "\n")
+            self.set_files.append(path)
+        return r
+
+    def getSetFiles(self):
+        return list(self.set_files)
+
+    def getSelectedSetFiles(self):
+        return [self.set_files[k] for k in self.result["kept"]]
+
+
 class ConcatenatedSequenceAlignment:
     """.../pepr/alignment/ConcatenatedSequenceAlignment.java's gene homoplasy test (:65-425) on the device (Context.gene_steps,
     Context.step_thresholds; the rules are in include/peprml.h).  In the reference nothing ever calls setStepsPerSite
