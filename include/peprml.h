@@ -1159,6 +1159,76 @@ int  pml_debug_mcl_steps(pml_ctx *ctx, int n, const double *matrix_in, const pml
  * loop included, by HIP events).  Never reset. */
 int  pml_mcl_stats(pml_ctx *ctx, long long *launches, double *total_ms);
 
+/* ---- Homology search: the all-vs-each Smith-Waterman hit table ----
+ * The table pml_homolog_groups starts from.  The reference makes it in PhyloPipeline.runBlast (:1061-1077) through BlastRunner
+ * (alignment/BlastRunner.java:539-599): `blastall -p blastp -d <genome g> -i <all proteins> -e 0.1 -v 1 -b 1 -m 8`, once per target
+ * genome.  Neither a BLAST binary nor its source is in the reference, so PARITY WITH blastall IS UNPINNED: this is the exact
+ * search BLAST approximates, every protein against every protein of every genome, and only the fields everything downstream
+ * reads (query id, subject id, bit score: filterHitPairFile :989-1024, filterForBidirectional :911-987) are claimed.
+ * Input: G genomes in the caller's order, each an ordered list of proteins.  A label is the first whitespace-delimited token of
+ * labels[i].  Residues are upper-cased; the codes of the BLOSUM62 table as loaded (pml_pairwise_scores' table576, same order:
+ * ARNDCQEGHILKMFPSTWYV B Z X) map to themselves, J O U map to X; `-` or any other byte is PML_EINVAL naming protein and position.
+ * A protein of length 0 is neither query nor subject; a length above 65 535 is PML_EINVAL.
+ * Score: Smith-Waterman with affine gaps, a gap of length k costs open + k * extend (defaults 11 and 1, blastp's "existence
+ * 11, extension 1"):  E[i][j] = max(E[i][j-1] - ext, H[i][j-1] - open - ext), F[i][j] the same along i,
+ * H[i][j] = max(0, H[i-1][j-1] + s(q_i, t_j), E[i][j], F[i][j]), S = max H.  Exact integers (int32) on the device, in the host
+ * twin and in tests/sw_ref.py.  Table entries must fit int8.
+ * Selection (-v 1 -b 1 per blastall run): for every query q (every protein of every genome) and every target genome g (its own
+ * included) the winner is the subject of g with the largest S, ties to the lowest position in g's order.  hits_per_query other
+ * than 0 / 1 is PML_EINVAL.
+ * Statistics, on the host in f64 from the integer S: bits = (lambda S - ln K) / ln 2, E = K m N exp(-lambda S), m the query
+ * length, N the total residues of genome g; defaults lambda 0.267, K 0.041 (BLOSUM62, 11/1, gapped).  A winner is a hit when
+ * E <= evalue (default 0.1, the Java's evalueCutoff) and S > 0.
+ * NOT BUILT: SEG masking, composition-based statistics, effective-length correction (no length adjustment is made), more than
+ * one HSP per pair, hits_per_query > 1, a k-mer prefilter or any non-exhaustive mode.
+ * Table: one line per hit, in the order of BlastRunner.getResults with one query set: target genome by target genome, within a
+ * target the queries in genome order, then file order.  Twelve tab-separated fields `qlabel slabel pident length mismatch
+ * gapopen qstart qend sstart send evalue bits`, evalue as %.2e, bits as %.1f.  With traceback = 0 fields 2..9 are `0`.  With
+ * traceback = 1 the host fills them from one optimal alignment of each hit (a host loop over the hits only): the end cell is
+ * the first maximal cell in row-major order (query rows outer); the walk back from H prefers the diagonal, then E, then F; inside
+ * E (F) the gap opens at this cell when E[i][j] = H[i][j-1] - open - ext, else extends; it stops at H = 0.  Coordinates are
+ * 1-based, length = columns, gapopen = gap runs, pident = 100 identical / length as %.2f (identity of the codes).
+ * Device (csrc/sw.hip): one lane group per (query, chunk of one genome's subjects), each lane a strip of T query rows in
+ * registers, the chunk's subjects streaming through the lanes back to back as a systolic anti-diagonal pipeline; classes by
+ * query length with groups of 16 / 32 / 64 lanes (pml_sw_class_limits), the widest in passes over a line buffer.  The winner
+ * per (query, genome) is kept on the device as a 64-bit key (S << 32 | 0xFFFFFFFF - position) under a global integer maximum:
+ * the nq x G keys are the only download. */
+typedef struct pml_sw_opts {
+    int gap_open, gap_extend;                         /* 0 = 11, 1 */
+    double lambda, K, evalue;                         /* 0 = 0.267, 0.041, 0.1 */
+    int hits_per_query, traceback;                    /* 0 or 1; 0 or 1 */
+    const int *table576;                              /* NULL = BLOSUM62 as loaded */
+} pml_sw_opts;
+typedef struct pml_proteome_set {
+    int ngenomes;
+    const int *genome_off;                            /* [ngenomes + 1] into labels / residues */
+    const char *const *labels;
+    const char *const *residues;                      /* NUL-terminated */
+} pml_proteome_set;
+typedef struct pml_sw_result {
+    long long nhits;
+    int *query, *subject;                             /* [nhits] global protein indices */
+    int *target_genome, *score;
+    double *bits, *evalue;
+    char *table; long long table_bytes;               /* the table text */
+    long long cells;                                  /* DP cells of the search: the sum of m n over all pairs */
+} pml_sw_result;
+int  pml_sw_search(pml_ctx *ctx, const pml_proteome_set *set, const pml_sw_opts *opts, pml_sw_result *result);
+/* the same rule in plain C++ loops, no context (csrc/sw_host.cpp): the CPU tests' subject and the timing baseline */
+int  pml_sw_search_host(const pml_proteome_set *set, const pml_sw_opts *opts, pml_sw_result *result);
+void pml_sw_result_free(pml_sw_result *result);
+/* limits_out[8] = per class lanes and the longest query of one pass (16 T, 32 T, 64 T; the last class takes longer ones in
+ * passes), then the strip T and the default chunk's stream bytes */
+int  pml_sw_class_limits(int *limits_out);
+/* test door: the raw score of every pair, no selection.  The subjects are treated as one genome (chunks and units as in a
+ * search).  force_class -1 = by length, 0 .. 2 = that class (PML_EINVAL when a query is longer than the class's one pass and
+ * the class is not the last); force_path 0 = int32, the only path built */
+int  pml_debug_sw_scores(pml_ctx *ctx, int nq, const char *const *queries, int ns, const char *const *subjects, const pml_sw_opts *opts,
+                         int force_class, int force_path, int *scores_out /* [nq][ns] */);
+/* launches[4] = k_sw_score launches per class and work units on this context so far, *cells the DP cells they covered; with
+ * cfg.profile = 1 total_ms[4] = the three classes and the uploads (HIP events).  Never reset. */
+int  pml_sw_stats(pml_ctx *ctx, long long *launches, long long *cells, double *total_ms);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);

@@ -45,7 +45,23 @@ SYMBOLS = [
     "pml_neighbor_masher", "pml_neighbor_masher_result_free",
     "pml_mcl_cluster", "pml_mcl_cluster_host", "pml_homolog_groups", "pml_homolog_groups_result_free", "pml_hits_filter_host",
     "pml_hits_bidirectional_host", "pml_homolog_select_host", "pml_mcl_class_limits", "pml_debug_mcl_steps", "pml_mcl_stats",
+    "pml_sw_search", "pml_sw_search_host", "pml_sw_result_free", "pml_sw_class_limits", "pml_debug_sw_scores", "pml_sw_stats",
 ]
+
+
+class SwOpts(C.Structure):
+    _fields_ = [("gap_open", C.c_int), ("gap_extend", C.c_int), ("lambda_", C.c_double), ("K", C.c_double), ("evalue", C.c_double),
+                ("hits_per_query", C.c_int), ("traceback", C.c_int), ("table576", C.POINTER(C.c_int))]
+
+
+class ProteomeSet(C.Structure):
+    _fields_ = [("ngenomes", C.c_int), ("genome_off", C.POINTER(C.c_int)), ("labels", C.POINTER(C.c_char_p)), ("residues", C.POINTER(C.c_char_p))]
+
+
+class SwResult(C.Structure):
+    _fields_ = [("nhits", C.c_longlong), ("query", C.POINTER(C.c_int)), ("subject", C.POINTER(C.c_int)), ("target_genome", C.POINTER(C.c_int)),
+                ("score", C.POINTER(C.c_int)), ("bits", C.POINTER(C.c_double)), ("evalue", C.POINTER(C.c_double)),
+                ("table", C.c_void_p), ("table_bytes", C.c_longlong), ("cells", C.c_longlong)]
 
 
 class MclOpts(C.Structure):
@@ -410,5 +426,13 @@ def load():
     L.pml_mcl_class_limits.argtypes = [ip]
     L.pml_debug_mcl_steps.argtypes = [vp, C.c_int, dp, mop, C.c_int, C.c_int, dp, dp]
     L.pml_mcl_stats.argtypes = [vp, lp, dp]
+    sop, psp, srp = C.POINTER(SwOpts), C.POINTER(ProteomeSet), C.POINTER(SwResult)
+    L.pml_sw_search.argtypes = [vp, psp, sop, srp]
+    L.pml_sw_search_host.argtypes = [psp, sop, srp]
+    L.pml_sw_result_free.argtypes = [srp]
+    L.pml_sw_result_free.restype = None
+    L.pml_sw_class_limits.argtypes = [ip]
+    L.pml_debug_sw_scores.argtypes = [vp, C.c_int, cpp, C.c_int, cpp, sop, C.c_int, C.c_int, ip]
+    L.pml_sw_stats.argtypes = [vp, lp, lp, dp]
     _lib = L
     return L

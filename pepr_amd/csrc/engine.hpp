@@ -59,6 +59,8 @@ struct Ctx {
     // pml_mcl_stats: k_mcl_fill, k_mcl_lds<packed>, k_mcl_lds, k_mcl_expand, k_mcl_inflate, k_mcl_flag, k_mcl_read launches and sub-batches;
     // (profile mode) HIP-event times of uploads and fill, the packed class, the LDS class, the HBM class
     long long mcl_launches[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double mcl_ms[4] = {0, 0, 0, 0};
+    // pml_sw_stats: k_sw_score launches per class and work units, the DP cells they covered; (profile mode) HIP-event times of the classes and the uploads
+    long long sw_launches[4] = {0, 0, 0, 0}, sw_cells = 0; double sw_ms[4] = {0, 0, 0, 0};
     std::vector<double> boot_last_lnl;                          // the ML replicates' lnL of the last pml_bootstrap2 call (pml_boot_replicate_lnls)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;

@@ -6,6 +6,7 @@
 #include "gblocks.hpp"
 #include "mash.hpp"
 #include "mcl.hpp"
+#include "sw.hpp"
 #include "treecmp.hpp"
 
 namespace pml {
@@ -425,5 +426,17 @@ void launch_mcl_inflate(const MclComp *comps, const int *active, int nactive, in
 void launch_mcl_flag(const MclComp *comps, const int *active, int nactive, const double *chaos_col, const MclRun &run, int it, int *iters, double *chaos, int *flag,
                      hipStream_t s);
 void launch_mcl_read(const MclComp *comps, int ncomps, int max_n, const double *pool, const int *iters, int *best, unsigned *mask, hipStream_t s);
+
+// Homology search (sw.hip; the rule is in include/peprml.h, the shared pieces in sw.hpp).  A chunk: `len` stream bytes at `off` of
+// the call's stream array (one genome's subjects back to back, SW_MARK behind each), its first subject in the per-subject
+// position array, its genome.  A query: its codes in the residue array, its row in best / dbg, and for a query of several
+// passes the offset (in int2) of its line buffers, where chunk c's begins at lb_at(c) - run.lb_base (-1: one pass, none)
+struct SwChunk { long long off; int len, sub0, genome, lb_at; };
+struct SwQuery { long long off; int len, index; long long lb_off; };
+struct SwRun { int oe, ext, G, nq, chunk0, pad; long long lb_base, dbg_ld; };
+// class cls: queries[0 .. run.nq) against chunks[run.chunk0 .. run.chunk0 + nchunks); best[index * G + genome] takes the
+// 64-bit maximum of the chunk's keys; dbg (test door, else null): dbg[index * dbg_ld + position] = the pair's score
+void launch_sw_score(int cls, const SwQuery *queries, const SwChunk *chunks, int nchunks, const SwRun &run, const uint8_t *codes, const uint8_t *stream,
+                     const int *sub_pos, const int8_t *table, int2 *linebuf, unsigned long long *best, int *dbg, hipStream_t s);
 
 }  // namespace pml

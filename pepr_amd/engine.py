@@ -917,6 +917,33 @@ class Context:
                 "flag_launches": n[5], "read_launches": n[6], "sub_batches": n[7],
                 "upload_fill_ms": ms[0], "packed_ms": ms[1], "lds_ms": ms[2], "hbm_ms": ms[3]}
 
+    # ---- homology search: the all-vs-each Smith-Waterman hit table (include/peprml.h "Homology search") ----
+    def sw_search(self, genomes, **opts):
+        """genomes: a list of genomes, each a list of (title, residues) in file order -> the hit table and its hits as
+        sw_search_host returns them.  Options as there."""
+        keep = []
+        st, o, r = _sw_set(genomes, keep), _sw_opts(opts, keep), _lib.SwResult()
+        self._check(self.L.pml_sw_search(self.ptr, C.byref(st), C.byref(o), C.byref(r)))
+        return _sw_result(r)
+
+    def debug_sw_scores(self, queries, subjects, force_class=-1, force_path=0, **opts):
+        """Test door: the raw score of every (query, subject) pair, no selection -> int32[nq][ns].  force_class 0 .. 2 runs
+        every query in that class."""
+        keep = []
+        qa = (C.c_char_p * max(len(queries), 1))(*[_sw_bytes(x) for x in queries])
+        sa = (C.c_char_p * max(len(subjects), 1))(*[_sw_bytes(x) for x in subjects])
+        out = np.zeros((len(queries), len(subjects)), dtype=np.int32)
+        o = _sw_opts(opts, keep)
+        self._check(self.L.pml_debug_sw_scores(self.ptr, len(queries), qa, len(subjects), sa, C.byref(o), int(force_class), int(force_path),
+                                               out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def sw_stats(self):
+        """k_sw_score launches per class and work units on this context so far, the DP cells they covered, and (profile mode) ms"""
+        n, cells, ms = (C.c_longlong * 4)(), C.c_longlong(), (C.c_double * 4)()
+        self._check(self.L.pml_sw_stats(self.ptr, n, C.byref(cells), ms))
+        return {"launches": [n[0], n[1], n[2]], "units": n[3], "cells": cells.value, "class_ms": [ms[0], ms[1], ms[2]], "upload_ms": ms[3]}
+
     # ---- the gene homoplasy test of ConcatenatedSequenceAlignment (include/peprml.h pml_gene_steps, pml_step_thresholds) ----
     def gene_steps(self, genes, newick):
         """Per-column Fitch steps of the concatenation of `genes` on `newick`, the least steps each column can take, and the
@@ -1730,6 +1757,68 @@ def mcl_class_limits():
     out = (C.c_int * 4)()
     _lib.load().pml_mcl_class_limits(out)
     return out[0], out[1], out[2]
+
+
+def _sw_bytes(x):
+    return x.encode("latin-1") if isinstance(x, str) else bytes(x)
+
+
+def _sw_set(genomes, keep):
+    off, labels, residues = [0], [], []
+    for g in genomes:
+        for title, res in g:
+            labels.append(_sw_bytes(title))
+            residues.append(_sw_bytes(res))
+        off.append(len(labels))
+    oa = (C.c_int * len(off))(*off)
+    la = (C.c_char_p * max(len(labels), 1))(*labels)
+    ra = (C.c_char_p * max(len(residues), 1))(*residues)
+    keep += [oa, la, ra]
+    return _lib.ProteomeSet(len(genomes), oa, la, ra)
+
+
+def _sw_opts(opts, keep):
+    bad = set(opts) - {"gap_open", "gap_extend", "lambda_", "K", "evalue", "hits_per_query", "traceback", "table"}
+    if bad:
+        raise TypeError("unknown option(s) " + ", ".join(sorted(bad)))
+    o = _lib.SwOpts(int(opts.get("gap_open", 0)), int(opts.get("gap_extend", 0)), float(opts.get("lambda_", 0.0)), float(opts.get("K", 0.0)),
+                    float(opts.get("evalue", 0.0)), int(opts.get("hits_per_query", 0)), int(bool(opts.get("traceback", False))), None)
+    if opts.get("table") is not None:
+        t = np.ascontiguousarray(opts["table"], dtype=np.int32).reshape(576)
+        keep.append(t)
+        o.table576 = t.ctypes.data_as(C.POINTER(C.c_int))
+    return o
+
+
+def _sw_result(r):
+    try:
+        n = r.nhits
+        return {"table": C.string_at(r.table, r.table_bytes), "cells": r.cells,
+                "query": [r.query[i] for i in range(n)], "subject": [r.subject[i] for i in range(n)],
+                "target_genome": [r.target_genome[i] for i in range(n)], "score": [r.score[i] for i in range(n)],
+                "bits": [r.bits[i] for i in range(n)], "evalue": [r.evalue[i] for i in range(n)]}
+    finally:
+        _lib.load().pml_sw_result_free(C.byref(r))
+
+
+def sw_search_host(genomes, **opts):
+    """Host only: Context.sw_search's rule in plain C++ loops (the CPU tests' subject and the timing baseline).  Options:
+    gap_open, gap_extend, lambda_, K, evalue (0 = 11, 1, 0.267, 0.041, 0.1), hits_per_query (0 / 1), traceback, table (576 ints).
+    -> {"table" (bytes, the twelve-field lines), "query", "subject" (global protein indices), "target_genome", "score", "bits",
+    "evalue" per hit, "cells"}"""
+    keep = []
+    st, o, r = _sw_set(genomes, keep), _sw_opts(opts, keep), _lib.SwResult()
+    rc = _lib.load().pml_sw_search_host(C.byref(st), C.byref(o), C.byref(r))
+    if rc:
+        raise PmlError(rc, "sw_search_host")
+    return _sw_result(r)
+
+
+def sw_class_limits():
+    """{"lanes": group widths per class, "rows": the longest query of one pass per class, "strip": T, "chunk": stream bytes}"""
+    out = (C.c_int * 8)()
+    _lib.load().pml_sw_class_limits(out)
+    return {"lanes": [out[0], out[2], out[4]], "rows": [out[1], out[3], out[5]], "strip": out[6], "chunk": out[7]}
 
 
 def mash_pair_host(a, b, s):

@@ -480,6 +480,56 @@ def readFastaRecords(path):
     return out
 
 
+class HomologySearch:
+    """BlastRunner (alignment/BlastRunner.java) for proteins, as PhyloPipeline.runBlast (:1061-1077) drives it: every protein of
+    every genome file against every genome, the best subject per query and target genome, as an exhaustive Smith-Waterman search
+    on the device (Context.sw_search; the rule, and that parity with blastall is unpinned, are in include/peprml.h).  Genome
+    files are read as createConcatenatedSet reads them (:199-208): lines of length <= 1 are dropped.  run() computes,
+    getResults() writes the combined table (result_file_name, else <run_name>_all_blast.out in out_dir, :427-478) and returns its path."""
+
+    def __init__(self, genome_files, evalue=0.1, run_name="run", ctx=None, out_dir=".", traceback=False, result_file_name=None):
+        self.genome_files, self.evalue, self.run_name, self.ctx = list(genome_files), float(evalue), run_name, ctx
+        self.out_dir, self.traceback, self.result_file_name = out_dir, bool(traceback), result_file_name
+        self.result, self.result_file = None, None
+
+    @staticmethod
+    def readGenome(path):
+        """[(title without '>', residues)] in file order"""
+        out = []
+        with open(path) as fh:
+            for line in fh.read().split("\n"):
+                line = line.rstrip("\r")
+                if len(line) <= 1:
+                    continue
+                if line.startswith(">"):
+                    out.append([line[1:], []])
+                elif out:
+                    out[-1][1].append(line.strip())
+        return [(t, "".join(r)) for t, r in out]
+
+    def setEvalueCutoff(self, evalue):
+        self.evalue = float(evalue)
+
+    def setRunName(self, name):
+        self.run_name = name
+
+    def run(self):
+        ctx = self.ctx or default_context()
+        self.result = ctx.sw_search([self.readGenome(p) for p in self.genome_files], evalue=self.evalue, traceback=self.traceback)
+        self.result_file = None
+        return self.result
+
+    def getResults(self):
+        if self.result is None:
+            self.run()
+        if self.result_file is None:
+            path = self.result_file_name or os.path.join(self.out_dir, self.run_name + "_all_blast.out")      # getResultFile :427-439
+            with open(path, "wb") as fh:
+                fh.write(self.result["table"])
+            self.result_file = path
+        return self.result_file
+
+
 class HomologGroups:
     """PhyloPipeline.java:357-406 between the all-vs-all search and the trees: filterHitPairFile or filterForBidirectional,
     `mcl --abc -I inflation` (runMCL :882-909) and SequenceSetExtractor's set files, with the clustering on the device

@@ -1,10 +1,13 @@
 #!/usr/bin/env python
 """PEPR's homolog-group step (PhyloPipeline.java:357-406) on the GPU engine: from the all-vs-all hit table to the set files.
 
-usage: pepr_homolog_groups.py -homology_search_method HITS.m8 -genome_file FASTA [FASTA ...] [-bidirectional true] [-inflation 1.5]
+usage: pepr_homolog_groups.py -homology_search_method HITS.m8|blast -genome_file FASTA [FASTA ...] [-bidirectional true] [-inflation 1.5]
                               [-run_name NAME] [-out_dir DIR] [-min_taxa N] [-max_taxa N] [-rep_only true] [-target_ntax N]
-                              [-target_min_gene N] [-device 0]
--homology_search_method  the tabular hit table (12 fields a line; the score is field 11), in place of the search the Java runs
+                              [-target_min_gene N] [-evalue 0.1] [-device 0]
+-homology_search_method  the tabular hit table (12 fields a line; the score is field 11), in place of the search the Java runs; or
+                         `blast` (HandyConstants.BLAST): the table is first made from the genome files by the exhaustive
+                         Smith-Waterman search (tree_builder.HomologySearch, -evalue 0.1) as <run_name>_all_blast.out in -out_dir
+                         (default: the working directory)
 -bidirectional           filterForBidirectional (:911-987) instead of filterHitPairFile (:989-1024)
 -inflation               mcl's -I
 Written, under the Java's names: HITS.m8_filtered or HITS.m8_bidir, <that>_mclOut (one cluster per line, labels joined by tabs), and
@@ -18,6 +21,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pepr_amd import engine, tree_builder
+
+
+BLAST = "blast"         # HandyConstants.BLAST
 
 
 def parse_args(argv):
@@ -43,7 +49,14 @@ def main(argv=None, ctx=None):
         sys.stderr.write(__doc__)
         return 2
     one = lambda k, d: args.get(k, [d])[0]      # noqa: E731
-    hg = tree_builder.HomologGroups(one("homology_search_method", None), args.get("genome_file", []), ctx=ctx or engine.Context(int(one("device", "0"))),
+    ctx = ctx or engine.Context(int(one("device", "0")))
+    hits = one("homology_search_method", None)
+    if hits == BLAST:
+        search = tree_builder.HomologySearch(args.get("genome_file", []), evalue=float(one("evalue", "0.1")), run_name=one("run_name", "run"), ctx=ctx,
+                                             out_dir=one("out_dir", "."))
+        hits = search.getResults()
+        print("%d hits -> %s" % (len(search.result["query"]), hits))
+    hg = tree_builder.HomologGroups(hits, args.get("genome_file", []), ctx=ctx,
                                     run_name=one("run_name", "run"), out_dir=args.get("out_dir", [None])[0],
                                     bidirectional=one("bidirectional", "false").lower() == "true", inflation=float(one("inflation", "1.5")),
                                     min_taxa=int(one("min_taxa", "0")), max_taxa=int(one("max_taxa", str(2 ** 31 - 1))),
