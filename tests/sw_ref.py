@@ -178,6 +178,50 @@ def mutate(rng, text, frac=0.05):
     return "".join(out)
 
 
+NO_P = PLAIN.replace("P", "")         # partners of a P flank: no P, no B Z X J O U, no lower case
+
+
+def gap_subjects(p, at, flank=12):
+    """pieces of p around row `at` with three residues cut out (the query's rows at - 1 .. at + 1 face a gap: F crosses the
+    boundary) and with three put in (E)"""
+    lo, hi = max(at - flank, 0), min(at + flank, len(p))
+    cut = p[lo:max(at - 1, lo)] + p[min(at + 2, hi):hi]
+    put = p[lo:at] + "WCW" + p[at:hi]
+    return [cut, put]
+
+
+def asym_tables(seed=62):
+    """two 24 x 24 tables that are not their own transpose: (mild) BLOSUM62 with 3 subtracted above the diagonal, (wild) seeded
+    uniform integers over all of int8 with both ends of the range planted, 127 on the diagonal too"""
+    mild = blosum62().copy()
+    mild[np.triu_indices(24, 1)] -= 3
+    wild = np.random.default_rng(seed).integers(-128, 128, (24, 24)).astype(np.int64)
+    wild[0][1], wild[1][0], wild[17][17] = 127, -128, 127
+    return mild, wild
+
+
+def flanked(core, total, at):
+    """core inside a run of P, `total` residues in all.  Against a partner out of NO_P every BLOSUM62 score of a P row is
+    negative: the rows before the core leave H = 0 and F below zero, the rows behind it never raise the maximum, so
+    score(flanked(core, total, at), s) == score(core, s), and the same with the flank on the subject's side"""
+    assert 0 <= at and at + len(core) <= total
+    return "P" * at + core + "P" * (total - at - len(core))
+
+
+def stream_chunks(lengths, chunk_bytes):
+    """the rule of DESIGN.md "Homology search" by which one genome's subjects are laid out: ordered by length (stably), a boundary
+    code behind each, a chunk closed before the subject that would take it past chunk_bytes (one longer subject is a chunk alone)
+    -> (stream bytes of every chunk, the chunk of every subject by file position)"""
+    order = sorted((k for k in range(len(lengths)) if lengths[k] > 0), key=lambda k: lengths[k])
+    sizes, where = [], {}
+    for k in order:
+        if not sizes or sizes[-1] + lengths[k] + 1 > chunk_bytes:
+            sizes.append(0)
+        sizes[-1] += lengths[k] + 1
+        where[k] = len(sizes) - 1
+    return sizes, where
+
+
 def planted_families(seed=5, ngenomes=3, nfam=3, length=60):
     rng = np.random.default_rng(seed)
     roots = [random_protein(rng, length, PLAIN) for _ in range(nfam)]

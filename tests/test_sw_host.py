@@ -15,7 +15,7 @@ import sw_ref as ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 NEW_SYMBOLS = ["pml_sw_search", "pml_sw_search_host", "pml_sw_result_free", "pml_sw_class_limits", "pml_debug_sw_scores", "pml_sw_stats"]
-from sw_ref import planted_families, random_protein
+from sw_ref import NO_P, PLAIN, asym_tables, flanked, mutate, planted_families, random_protein
 
 
 def one_pair(q, t, **opts):
@@ -71,6 +71,66 @@ def test_gap_costs_and_table():
     t[17][8] = 3                                                       # asymmetric: W against H
     assert one_pair("AAWA", "AAHA", table=t) == ref.score("AAWA", "AAHA", table=t)
     assert one_pair("AAHA", "AAWA", table=t) == ref.score("AAHA", "AAWA", table=t)
+
+
+def test_asymmetric_tables_both_ways_round():
+    """table[query residue][subject residue]: on tables that are not their own transpose, one of them with both ends of int8"""
+    rng = np.random.default_rng(29)
+    pairs = [(random_protein(rng, int(m)), random_protein(rng, int(n))) for m, n in rng.integers(1, 61, (30, 2))]
+    pairs = [(q, s) if k % 2 else (q, mutate(rng, q, 0.4)) for k, (q, s) in enumerate(pairs)]    # every other pair related: mismatches inside the alignment
+    for name, t in zip(("mild", "wild"), asym_tables()):
+        assert (t != t.T).any() and t.min() >= -128 and t.max() <= 127
+        tt = np.ascontiguousarray(t.T)
+        changed = 0
+        for q, s in pairs:
+            want, back = ref.score(q, s, table=t), ref.score(s, q, table=t)
+            assert one_pair(q, s, table=t) == want, (name, q, s)
+            assert one_pair(s, q, table=t) == back, (name, s, q)
+            assert ref.score(s, q, table=tt) == want and one_pair(s, q, table=tt) == want        # S(q, s, T) == S(s, q, T^T)
+            changed += ref.score(q, s, table=tt) != want
+        print(name, "table: the transpose changes", changed, "of", len(pairs), "scores")
+        assert 2 * changed >= len(pairs)                              # the pairs tell a table from its transpose
+    wild = asym_tables()[1]
+    assert (wild[0][1], wild[1][0], wild[17][17]) == (127, -128, 127)
+    assert one_pair("AW", "RW", table=wild) == ref.score("AW", "RW", table=wild) == 254
+    assert one_pair("RW", "AW", table=wild) == ref.score("RW", "AW", table=wild) == 127
+
+
+def test_gap_costs_at_the_documented_limit():
+    rng = np.random.default_rng(31)
+    p = random_protein(rng, 60, PLAIN)
+    q, s = p, p[:30] + p[33:]                                          # three residues of the query face a gap
+    big = 1 << 20
+    got = {}
+    for go, ge in ((big, big), (1, big), (big, 1), (1, 1)):
+        got[go, ge] = ref.score(q, s, gap_open=go, gap_extend=ge)
+        assert one_pair(q, s, gap_open=go, gap_extend=ge) == got[go, ge], (go, ge)
+        assert one_pair(s, q, gap_open=go, gap_extend=ge) == ref.score(s, q, gap_open=go, gap_extend=ge) == got[go, ge], (go, ge)
+    assert got[1, 1] > got[big, 1] == got[1, big] == got[big, big] > 0  # only the cheap gap is taken
+    for opts in ({"gap_open": big + 1}, {"gap_extend": big + 1}):
+        with pytest.raises(engine.PmlError) as e:
+            engine.sw_search_host([[("t", s)], [("q", q)]], **opts)
+        assert e.value.code == engine.EINVAL
+
+
+def test_flank_identity():
+    """score(flanked(core), s) == score(core, s) for s out of NO_P: what makes the expectations of very long sequences cheap"""
+    rng = np.random.default_rng(37)
+    total = 2000
+    table = ref.blosum62()
+    assert (table[ref.ORDER.index("P")][ref.encode(NO_P)] < 0).all() and (table[ref.encode(NO_P), ref.ORDER.index("P")] < 0).all()
+    for n in (40, 73, 100):
+        core = random_protein(rng, n)
+        piece = "".join(c if c in NO_P else "A" for c in mutate(rng, core.upper(), 0.2)[5:35])
+        s = random_protein(rng, 20, NO_P) + piece + random_protein(rng, 10, NO_P)                 # a relative of the core, free of P
+        assert not set(s) - set(NO_P)
+        want, back = ref.score(core, s), ref.score(s, core)
+        assert want > 40
+        for at in (0, 777, total - n):
+            f = flanked(core, total, at)
+            assert len(f) == total and f[at:at + n] == core
+            assert ref.score(f, s) == want and one_pair(f, s) == want, (n, at)             # the flank on the query's side
+            assert ref.score(s, f) == back and one_pair(s, f) == back, (n, at)             # ... and on the subject's
 
 
 def test_random_proteins():
