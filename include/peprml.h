@@ -1229,6 +1229,90 @@ int  pml_debug_sw_scores(pml_ctx *ctx, int nq, const char *const *queries, int n
  * cfg.profile = 1 total_ms[4] = the three classes and the uploads (HIP events).  Never reset. */
 int  pml_sw_stats(pml_ctx *ctx, long long *launches, long long *cells, double *total_ms);
 
+/* ---- Multiple alignment: progressive profile alignment of the selected sets ----
+ * The step between pml_homolog_groups' set_<k>.faa files and everything that starts from aligned genes.  The reference does it in
+ * PhylogenomicPipeline2.alignAll (:701-725) and getAlignment (:737-806) through MultipleSequenceAligner.getMSA (:90-141), which
+ * runs `muscle -fasta -stable -quiet`, and getProfileMSA (:143-218), which runs `muscle -profile -in1 -in2`.  muscle is in the
+ * reference as a binary without source, so PARITY WITH muscle IS UNPINNED: the alignment is rebuilt from the rule below, in exact
+ * integers on the device, in the host twin (csrc/msa_host.cpp) and in tests/msa_ref.py.
+ * Input: a set is n >= 1 proteins in the caller's order.  Residues are encoded as the homology search encodes them (23 codes,
+ * J O U -> X); any other byte is PML_EINVAL naming sequence and position, and so is a sequence of length 0.  table576 (NULL =
+ * BLOSUM62 as loaded) must fit int8 and need not be symmetric; gap_open / gap_extend 0 = 11 / 1.
+ * Guide tree: S(a, b), a < b, is the homology search's Smith-Waterman score of a as the query against b as the subject (same
+ * table and costs; k_sw_score on the device, sw_score_host in the twin).  Clusters start as single sequences; a cluster's id is
+ * its lowest member index.  Until one cluster remains the pair of clusters with the largest average of S over its cross pairs is
+ * merged; two averages are compared exactly (Sum_AB |C||D| against Sum_CD |A||B| in 128-bit integers), ties go to the lowest
+ * first id, then the lowest second id.  In a merge the cluster with the lower id is X, the other Y; the merged rows are X's rows,
+ * then Y's rows.  A merge's level is 1 + the larger level of its two clusters, single sequences 0.
+ * Profile alignment of X (nX rows, LX columns) and Y (nY rows, LY columns): w = nX nY, GO = gap_open w, GE = gap_extend w,
+ * s(i, j) = Sum_a Sum_b cX[i][a] cY[j][b] T[a][b] over the 23 codes, cX[i][a] the rows of X with code a in column i (gap cells add
+ * nothing).  A gap run before the first or behind the last column of the other profile pays no open cost: oE(i) = 0 for i in
+ * {0, LX}, else GO; oF(j) = 0 for j in {0, LY}, else GO.
+ *   H[0][0] = 0
+ *   E[i][j] = max(E[i][j-1] - GE, H[i][j-1] - oE(i) - GE)     j >= 1   (a column of Y against gaps in X)
+ *   F[i][j] = max(F[i-1][j] - GE, H[i-1][j] - oF(j) - GE)     i >= 1   (a column of X against gaps in Y)
+ *   H[i][j] = max(H[i-1][j-1] + s(i, j), E[i][j], F[i][j])             terms that do not exist are minus infinity
+ *   score   = H[LX][LY]
+ * Traceback from (LX, LY): in H the diagonal is preferred, then E, then F; inside E the run opens at this cell when
+ * E[i][j] = H[i][j-1] - oE(i) - GE, else it extends; F likewise.
+ * Cells are int32.  A merge is refused (PML_EINVAL naming the set and the bound) when
+ *   w ((M + gap_open) (min(LX, LY) + 1) + gap_extend (LX + LY)) >= 2^30,   M the largest |table entry|,
+ * checked on the host with the two profiles' actual lengths before the merge is launched; an int64 path is not built.  Minus
+ * infinity is -2^30.  Only E[i][0] and F[0][j] hold it.  Every other cell is the score of a real path: it is at most w M min(LX,
+ * LY) and at least -(GE (LX + LY) + 2 GO), both inside the bound, so it is above -2^30, and minus infinity less one GE (the most
+ * it is lowered by before a real term replaces it) never wins or ties a maximum and stays above -2^31.
+ * The counts and V_j[a] = Sum_b cY[j][b] T[a][b] are int16 on the device: a merge with nX > 32767 or nY > 255 is PML_EINVAL (no
+ * int32 count path is built).
+ * Output (-stable): the rows in input order, all of one length, `-` for a gap, residues as encoded (upper case, J O U as X).  A set
+ * of one sequence is that sequence.
+ * NOT BUILT: muscle's k-mer distances, its second (Kimura) tree, refinement by tree bipartitioning, its log-expectation score and
+ * position-specific gap costs, anchors and diagonals, Hirschberg or any linear-space mode.
+ * Device (csrc/msa.hip): the pair scores come from the homology search's driver, consecutive sets sharing a call until they hold 96
+ * sequences.  All merges of one level of all sets of a call go through one round of launches: k_msa_colv (V_j of every
+ * Y), k_msa_dp (lane groups of 16 / 32 / 64 lanes by LX, a lane a strip of T = 8 columns of X in registers, Y's columns
+ * streaming through the lanes; one direction word per strip and column: H source, E opened, F opened, four bits a cell),
+ * k_msa_walk (the traceback, one lane per merge, writes the merged column map) and k_msa_gather (the merged rows and counts).
+ * Between levels only the merged lengths come back.  The direction words live in an HBM scratch; a level is cut into sub-batches
+ * under the scratch budget (half the HBM budget, or PML_MSA_SCRATCH_BYTES), and a single merge above it is PML_ENOMEM. */
+typedef struct pml_msa_opts {
+    int gap_open, gap_extend;                         /* 0 = 11, 1 */
+    const int *table576;                              /* NULL = BLOSUM62 as loaded */
+} pml_msa_opts;
+typedef struct pml_msa_set {
+    int nseq;
+    const char *const *residues;                      /* NUL-terminated; in a profile `-` is a gap */
+} pml_msa_set;
+typedef struct pml_msa_result {
+    int nrows, ncols;
+    char *rows;                                       /* nrows x (ncols + 1): every row NUL-terminated */
+    int nmerges;                                      /* nrows - 1 (pml_msa_align), 1 (profile calls) */
+    int *merge_x, *merge_y, *merge_level;             /* cluster ids in the order of the merges, and their levels */
+    long long *merge_score;                           /* H[LX][LY] of every merge */
+    unsigned char *path;                              /* profile calls: per merged column 0 = both, 1 = Y's column only, 2 = X's only; else NULL */
+} pml_msa_result;
+/* results[nsets].  On an error every result is empty. */
+int  pml_msa_align(pml_ctx *ctx, int nsets, const pml_msa_set *sets, const pml_msa_opts *opts, pml_msa_result *results);
+/* the same rule in plain C++ loops, no context (csrc/msa_host.cpp): the CPU tests' subject and the timing baseline.  err (may
+ * be NULL) receives the message of a failure, at most err_cap bytes with the NUL */
+int  pml_msa_align_host(int nsets, const pml_msa_set *sets, const pml_msa_opts *opts, pml_msa_result *results, char *err, int err_cap);
+/* two given alignments (getProfileMSA): a is X, b is Y; rows of equal length, `-` a gap.  The merged rows are a's, then b's */
+int  pml_msa_profile_align(pml_ctx *ctx, const pml_msa_set *a, const pml_msa_set *b, const pml_msa_opts *opts, long long *score_out, pml_msa_result *result);
+int  pml_msa_profile_align_host(const pml_msa_set *a, const pml_msa_set *b, const pml_msa_opts *opts, long long *score_out, pml_msa_result *result,
+                                char *err, int err_cap);
+/* the merges of a set of n sequences from its pair scores (scores[a * n + b], a < b, is read): n - 1 merges */
+int  pml_msa_guide_tree_host(int n, const long long *scores, int *merge_x, int *merge_y, int *merge_level);
+void pml_msa_result_free(pml_msa_result *result);
+/* limits_out[8] = per class lanes and the columns of X of one pass (16 T, 32 T, 64 T; the last class takes longer ones in
+ * passes over a line buffer), then the strip T and the threads of a workgroup */
+int  pml_msa_limits(int *limits_out);
+/* test door: pml_msa_profile_align with the class forced (-1 = by LX; PML_EINVAL when X is longer than the class's one pass and
+ * the class is not the last) */
+int  pml_debug_msa_profile_align(pml_ctx *ctx, const pml_msa_set *a, const pml_msa_set *b, const pml_msa_opts *opts, int force_class, long long *score_out,
+                                 pml_msa_result *result);
+/* counts[8] = k_msa_colv, k_msa_dp, k_msa_walk, k_msa_gather launches, merges, levels, sub-batches and DP cells on this context
+ * so far; with cfg.profile = 1 total_ms[4] = the four kernels (HIP events).  Never reset. */
+int  pml_msa_stats(pml_ctx *ctx, long long *counts, double *total_ms);
+
 /* Concurrent pml_score / pml_optimize / pml_search calls on one context (PEPR's tree_threads workers) are
  * coalesced into device batches; this reports how many batches ran and how many single calls they carried. */
 int pml_coalescing_stats(pml_ctx *ctx, long long *batches, long long *requests);

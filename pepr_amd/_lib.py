@@ -46,7 +46,23 @@ SYMBOLS = [
     "pml_mcl_cluster", "pml_mcl_cluster_host", "pml_homolog_groups", "pml_homolog_groups_result_free", "pml_hits_filter_host",
     "pml_hits_bidirectional_host", "pml_homolog_select_host", "pml_mcl_class_limits", "pml_debug_mcl_steps", "pml_mcl_stats",
     "pml_sw_search", "pml_sw_search_host", "pml_sw_result_free", "pml_sw_class_limits", "pml_debug_sw_scores", "pml_sw_stats",
+    "pml_msa_align", "pml_msa_align_host", "pml_msa_profile_align", "pml_msa_profile_align_host", "pml_msa_guide_tree_host",
+    "pml_msa_result_free", "pml_msa_limits", "pml_debug_msa_profile_align", "pml_msa_stats",
 ]
+
+
+class MsaOpts(C.Structure):
+    _fields_ = [("gap_open", C.c_int), ("gap_extend", C.c_int), ("table576", C.POINTER(C.c_int))]
+
+
+class MsaSet(C.Structure):
+    _fields_ = [("nseq", C.c_int), ("residues", C.POINTER(C.c_char_p))]
+
+
+class MsaResult(C.Structure):
+    _fields_ = [("nrows", C.c_int), ("ncols", C.c_int), ("rows", C.c_void_p), ("nmerges", C.c_int),
+                ("merge_x", C.POINTER(C.c_int)), ("merge_y", C.POINTER(C.c_int)), ("merge_level", C.POINTER(C.c_int)),
+                ("merge_score", C.POINTER(C.c_longlong)), ("path", C.POINTER(C.c_ubyte))]
 
 
 class SwOpts(C.Structure):
@@ -434,5 +450,16 @@ def load():
     L.pml_sw_class_limits.argtypes = [ip]
     L.pml_debug_sw_scores.argtypes = [vp, C.c_int, cpp, C.c_int, cpp, sop, C.c_int, C.c_int, ip]
     L.pml_sw_stats.argtypes = [vp, lp, lp, dp]
+    mo, ms, mr = C.POINTER(MsaOpts), C.POINTER(MsaSet), C.POINTER(MsaResult)
+    L.pml_msa_align.argtypes = [vp, C.c_int, ms, mo, mr]
+    L.pml_msa_align_host.argtypes = [C.c_int, ms, mo, mr, C.c_char_p, C.c_int]
+    L.pml_msa_profile_align.argtypes = [vp, ms, ms, mo, lp, mr]
+    L.pml_msa_profile_align_host.argtypes = [ms, ms, mo, lp, mr, C.c_char_p, C.c_int]
+    L.pml_msa_guide_tree_host.argtypes = [C.c_int, lp, ip, ip, ip]
+    L.pml_msa_result_free.argtypes = [mr]
+    L.pml_msa_result_free.restype = None
+    L.pml_msa_limits.argtypes = [ip]
+    L.pml_debug_msa_profile_align.argtypes = [vp, ms, ms, mo, C.c_int, lp, mr]
+    L.pml_msa_stats.argtypes = [vp, lp, dp]
     _lib = L
     return L

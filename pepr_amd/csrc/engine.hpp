@@ -61,6 +61,9 @@ struct Ctx {
     long long mcl_launches[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double mcl_ms[4] = {0, 0, 0, 0};
     // pml_sw_stats: k_sw_score launches per class and work units, the DP cells they covered; (profile mode) HIP-event times of the classes and the uploads
     long long sw_launches[4] = {0, 0, 0, 0}, sw_cells = 0; double sw_ms[4] = {0, 0, 0, 0};
+    // pml_msa_stats: k_msa_colv, k_msa_dp, k_msa_walk, k_msa_gather launches (k_msa_counts, one a call, with the first), merges, levels,
+    // sub-batches, DP cells; (profile mode) HIP-event times of the four
+    long long msa_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double msa_ms[4] = {0, 0, 0, 0};
     std::vector<double> boot_last_lnl;                          // the ML replicates' lnL of the last pml_bootstrap2 call (pml_boot_replicate_lnls)
     struct Ev { int kind; hipEvent_t a, b; };
     std::vector<Ev> pending;

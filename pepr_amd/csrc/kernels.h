@@ -439,4 +439,24 @@ struct SwRun { int oe, ext, G, nq, chunk0, pad; long long lb_base, dbg_ld; };
 void launch_sw_score(int cls, const SwQuery *queries, const SwChunk *chunks, int nchunks, const SwRun &run, const uint8_t *codes, const uint8_t *stream,
                      const int *sub_pos, const int8_t *table, int2 *linebuf, unsigned long long *best, int *dbg, hipStream_t s);
 
+// Multiple alignment (msa.hip; the rule is in include/peprml.h, the shared pieces in msa.hpp).  A cluster's rows are n x L codes
+// (row major, MSA_GAP in a gap cell), its counts and a V are 12 dwords a column: 24 int16, code a in half a & 1 of dword a / 2.
+// A task is one merge: dir = its npass x (LY + lanes - 1) x lanes direction words, word ((pass * (LY + lanes - 1) + step) * lanes
+// + lane), step = column + lane; lb = two line buffers of LY (H, F) pairs (null: one pass); map = LX + LY (column of X, column of
+// Y) pairs, -1 for a gap, filled from the end; info[task] = (merged length, score)
+struct MsaCluster { const uint8_t *rows; uint32_t *cnt; int n, L; };
+struct MsaTask {
+    const uint8_t *x_rows, *y_rows; uint8_t *out_rows;
+    const uint32_t *x_cnt, *y_cnt; uint32_t *out_cnt;
+    uint32_t *v, *dir;
+    int2 *lb, *map;
+    int LX, LY, nX, nY, GO, GE, cls, pad;
+};
+struct MsaBlock { int first, count, cls, pad; };      // a workgroup of k_msa_dp: tasks[first .. first + count) of one class, count <= 64 / lanes
+void launch_msa_counts(const MsaCluster *clusters, int nclusters, int max_L, hipStream_t s);
+void launch_msa_colv(const MsaTask *tasks, int ntasks, int max_LY, const int8_t *table576, hipStream_t s);
+void launch_msa_dp(const MsaTask *tasks, const MsaBlock *blocks, int nblocks, int2 *info, hipStream_t s);
+void launch_msa_walk(const MsaTask *tasks, int ntasks, int2 *info, hipStream_t s);
+void launch_msa_gather(const MsaTask *tasks, int ntasks, int max_L, const int2 *info, hipStream_t s);
+
 }  // namespace pml

@@ -176,6 +176,16 @@ template <class F> int guarded(pml_ctx *pctx, F f) {
 
 }  // namespace
 
+namespace pml {
+int sw_scores_encoded(Ctx *ctx, const uint8_t *codes, const long long *off, const int *len, int n, const SwOpts &o, std::vector<int> &scores) {
+    Queries Q; Q.codes = codes + off[0]; Q.code_bytes = (size_t)(off[n - 1] + len[n - 1] - off[0]);
+    std::vector<std::vector<Subject>> genomes(1);
+    for (int i = 0; i < n; ++i) { Q.off.push_back(off[i] - off[0]); Q.len.push_back(len[i]); genomes[0].push_back({codes + off[i], len[i], i}); }
+    std::vector<unsigned long long> best;
+    return score_all(ctx, Q, genomes, o, -1, best, &scores, n);
+}
+}  // namespace pml
+
 extern "C" int pml_sw_search(pml_ctx *pctx, const pml_proteome_set *set, const pml_sw_opts *opts, pml_sw_result *result) {
     if (result) std::memset(result, 0, sizeof *result);
     if (!pctx || !set || !result) return PML_EINVAL;

@@ -53,4 +53,9 @@ int sw_score_host(const uint8_t *q, int m, const uint8_t *t, int n, const SwOpts
 int sw_finish(const SwSet &s, const SwOpts &o, const std::vector<unsigned long long> &best, long long cells, pml_sw_result *res, std::string &err);
 long long sw_total_cells(const SwSet &s);
 
+// the raw scores of n encoded sequences against each other through the search's launch path (sw.cpp, the driver under
+// pml_debug_sw_scores): scores[a * n + b] = a as the query against b as the subject.  The caller holds the context
+struct Ctx;
+int sw_scores_encoded(Ctx *ctx, const uint8_t *codes, const long long *off, const int *len, int n, const SwOpts &o, std::vector<int> &scores);
+
 }  // namespace pml

@@ -938,6 +938,37 @@ class Context:
                                                out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
+    def msa_align(self, sets, **opts):
+        """Multiple alignment of many sets in one call (include/peprml.h "Multiple alignment"): sets = a list of lists of residue
+        texts.  Options: gap_open, gap_extend (0 = 11, 1), table (576 ints).  -> one {"rows" (aligned texts in input order),
+        "merges" [(x, y, level, score)]} per set, as msa_align_host returns them"""
+        keep = []
+        sa, o = _msa_sets(sets, keep), _msa_opts(opts, keep)
+        res = (_lib.MsaResult * max(len(sets), 1))()
+        self._check(self.L.pml_msa_align(self.ptr, len(sets), sa, C.byref(o), res))
+        return [_msa_result(res[i]) for i in range(len(sets))]
+
+    def msa_profile_align(self, a, b, force_class=-1, **opts):
+        """Two alignments (lists of equally long rows, `-` a gap) aligned as profiles: a is X, b is Y.  -> {"score", "rows" (a's
+        rows, then b's), "path" (per merged column 0 both, 1 b's column only, 2 a's only), "merges"}.  force_class (test door):
+        the kernel's class, -1 = by a's length"""
+        keep = []
+        sa, sb, o, r, sc = _msa_sets([a], keep), _msa_sets([b], keep), _msa_opts(opts, keep), _lib.MsaResult(), C.c_longlong()
+        if force_class == -1:
+            self._check(self.L.pml_msa_profile_align(self.ptr, sa, sb, C.byref(o), C.byref(sc), C.byref(r)))
+        else:
+            self._check(self.L.pml_debug_msa_profile_align(self.ptr, sa, sb, C.byref(o), int(force_class), C.byref(sc), C.byref(r)))
+        out = _msa_result(r)
+        out["score"] = sc.value
+        return out
+
+    def msa_stats(self):
+        """{"launches": k_msa_colv, k_msa_dp, k_msa_walk, k_msa_gather launches on this context so far, "merges", "levels",
+        "sub_batches", "cells", "ms": (profile mode) the four kernels' HIP-event times}"""
+        n, ms = (C.c_longlong * 8)(), (C.c_double * 4)()
+        self._check(self.L.pml_msa_stats(self.ptr, n, ms))
+        return {"launches": [n[i] for i in range(4)], "merges": n[4], "levels": n[5], "sub_batches": n[6], "cells": n[7], "ms": [ms[i] for i in range(4)]}
+
     def sw_stats(self):
         """k_sw_score launches per class and work units on this context so far, the DP cells they covered, and (profile mode) ms"""
         n, cells, ms = (C.c_longlong * 4)(), C.c_longlong(), (C.c_double * 4)()
@@ -1812,6 +1843,83 @@ def sw_search_host(genomes, **opts):
     if rc:
         raise PmlError(rc, "sw_search_host")
     return _sw_result(r)
+
+
+def _msa_sets(sets, keep):
+    arr = (_lib.MsaSet * max(len(sets), 1))()
+    for i, st in enumerate(sets):
+        ra = (C.c_char_p * max(len(st), 1))(*[_sw_bytes(x) for x in st])
+        keep.append(ra)
+        arr[i] = _lib.MsaSet(len(st), ra)
+    keep.append(arr)
+    return arr
+
+
+def _msa_opts(opts, keep):
+    bad = set(opts) - {"gap_open", "gap_extend", "table"}
+    if bad:
+        raise TypeError("unknown option(s) " + ", ".join(sorted(bad)))
+    o = _lib.MsaOpts(int(opts.get("gap_open", 0)), int(opts.get("gap_extend", 0)), None)
+    if opts.get("table") is not None:
+        t = np.ascontiguousarray(opts["table"], dtype=np.int32).reshape(576)
+        keep.append(t)
+        o.table576 = t.ctypes.data_as(C.POINTER(C.c_int))
+    return o
+
+
+def _msa_result(r):
+    try:
+        rows = [C.string_at(r.rows + i * (r.ncols + 1), r.ncols).decode("latin-1") for i in range(r.nrows)]
+        out = {"rows": rows, "merges": [(r.merge_x[m], r.merge_y[m], r.merge_level[m], r.merge_score[m]) for m in range(r.nmerges)]}
+        if r.path:
+            out["path"] = [r.path[c] for c in range(r.ncols)]
+        return out
+    finally:
+        _lib.load().pml_msa_result_free(C.byref(r))
+
+
+def msa_align_host(sets, **opts):
+    """Host only: Context.msa_align's rule in plain C++ loops (the CPU tests' subject and the timing baseline)"""
+    keep = []
+    sa, o = _msa_sets(sets, keep), _msa_opts(opts, keep)
+    res = (_lib.MsaResult * max(len(sets), 1))()
+    err = C.create_string_buffer(512)
+    rc = _lib.load().pml_msa_align_host(len(sets), sa, C.byref(o), res, err, 512)
+    if rc:
+        raise PmlError(rc, err.value.decode("latin-1"))
+    return [_msa_result(res[i]) for i in range(len(sets))]
+
+
+def msa_profile_align_host(a, b, **opts):
+    """Host only: Context.msa_profile_align's rule in plain C++ loops"""
+    keep = []
+    sa, sb, o, r, sc = _msa_sets([a], keep), _msa_sets([b], keep), _msa_opts(opts, keep), _lib.MsaResult(), C.c_longlong()
+    err = C.create_string_buffer(512)
+    rc = _lib.load().pml_msa_profile_align_host(sa, sb, C.byref(o), C.byref(sc), C.byref(r), err, 512)
+    if rc:
+        raise PmlError(rc, err.value.decode("latin-1"))
+    out = _msa_result(r)
+    out["score"] = sc.value
+    return out
+
+
+def msa_guide_tree_host(scores):
+    """Host only: the merges [(x, y, level)] of a set from its n x n pair scores (the entries above the diagonal are read)"""
+    s = np.ascontiguousarray(scores, dtype=np.int64)
+    n = s.shape[0]
+    assert s.shape == (n, n)
+    x, y, lv = (C.c_int * max(n - 1, 1))(), (C.c_int * max(n - 1, 1))(), (C.c_int * max(n - 1, 1))()
+    rc = _lib.load().pml_msa_guide_tree_host(n, s.ctypes.data_as(C.POINTER(C.c_longlong)), x, y, lv)
+    if rc:
+        raise PmlError(rc, "msa_guide_tree_host")
+    return [(x[m], y[m], lv[m]) for m in range(n - 1)]
+
+
+def msa_limits():
+    """{"lanes": group widths per class, "rows": the columns of X of one pass per class, "strip": T, "threads": a workgroup}"""
+    out = (C.c_int * 8)()
+    _lib.load().pml_msa_limits(out)
+    return {"lanes": [out[0], out[2], out[4]], "rows": [out[1], out[3], out[5]], "strip": out[6], "threads": out[7]}
 
 
 def sw_class_limits():

@@ -530,6 +530,45 @@ class HomologySearch:
         return self.result_file
 
 
+ALIGNMENT_FILE_SUFFIX = "_align"        # HandyConstants.ALIGNMENT_FILE_SUFFIX
+
+
+class MultipleSequenceAligner:
+    """.../pepr/alignment/MultipleSequenceAligner.java: getMSA (:90-141, `muscle -fasta -stable -quiet`) and getProfileMSA
+    (:143-218, `muscle -profile -in1 -in2`) as the progressive profile alignment of include/peprml.h ("Multiple alignment") on the
+    device (Context.msa_align, Context.msa_profile_align); parity with muscle is unpinned.  Sequences are (title, residues) pairs
+    or a SequenceAlignment of unaligned rows; the result's rows are in input order (-stable) and it is named as the Java names
+    it: the input's name + "_align" (a null name reads "null_align").  getMSAs aligns many sets in ONE batched call.  host=True
+    runs the host twin (no device)."""
+
+    def __init__(self, ctx=None, host=False, **opts):
+        self.ctx, self.host, self.opts = ctx, bool(host), dict(opts)
+
+    @staticmethod
+    def _unpack(sequences):
+        if isinstance(sequences, SequenceAlignment):
+            return sequences.getTaxa(), list(sequences.rows), sequences.getName()
+        return [t for t, _ in sequences], [r for _, r in sequences], getattr(sequences, "name", None)
+
+    @staticmethod
+    def _named(name):
+        return ("null" if name is None else name) + ALIGNMENT_FILE_SUFFIX
+
+    def getMSAs(self, list_of_sets, names=None):
+        sets = [self._unpack(s) for s in list_of_sets]
+        rows = [r for _, r, _ in sets]
+        res = engine.msa_align_host(rows, **self.opts) if self.host else (self.ctx or default_context()).msa_align(rows, **self.opts)
+        return [SequenceAlignment(taxa, r["rows"], self._named(names[k] if names else name)) for k, ((taxa, _, name), r) in enumerate(zip(sets, res))]
+
+    def getMSA(self, sequences):
+        return self.getMSAs([sequences])[0]
+
+    def getProfileMSA(self, a, b):
+        f = engine.msa_profile_align_host if self.host else (self.ctx or default_context()).msa_profile_align
+        r = f(list(a.rows), list(b.rows), **self.opts)
+        return SequenceAlignment(list(a.getTaxa()) + list(b.getTaxa()), r["rows"], self._named(a.getName()))
+
+
 class HomologGroups:
     """PhyloPipeline.java:357-406 between the all-vs-all search and the trees: filterHitPairFile or filterForBidirectional,
     `mcl --abc -I inflation` (runMCL :882-909) and SequenceSetExtractor's set files, with the clustering on the device
